@@ -19,9 +19,11 @@ character-vs-character exchange (one RCCL all-gather of capsule state per step).
 `--scene` and `--mesh` choose the static scene and the skinned mesh independently.
 
 Rank 0 prints ONE JSON line. `roofline` prices the LBS kernel (the HBM-bound kernel of the
-path) from HIP events recorded on the stream it runs on; `cpu_baseline` times the CPU oracle
-(a float32 port of the reference's Swift path, which cannot be built here) on a bounded
-sample of the same crowd, on this box's host cores.
+path) from HIP events recorded on the stream it runs on. A plain run sets up, warms up, times
+the steps and prints the line; `--dump-outputs DIR` also writes what the last timed step left.
+`--full` adds the legs that are runs of their own outside the timed region: `lbs_alone`,
+`world_sync`, `real_mesh` and `cpu_baseline`, which times the CPU oracle (a float32 port of the
+reference's Swift path) on a bounded sample of the same crowd, on the host's cores.
 """
 import argparse
 import importlib
@@ -97,9 +99,17 @@ def main():
                          "GPUCharacterStepSystem.fixedUpdate — pinned push of every character's intent, tick, asynchronous pull of bodies + controllers + "
                          "locomotion + actions, wait for it, copy into host arrays — every step (metric name says so; not the headline)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the legs outside the timed region that the default N=1 line carries: `world_sync` (the drop-in loop beside the resident "
+                    help="with --full: skip the legs outside the timed region that its N=1 line carries: `world_sync` (the drop-in loop beside the resident "
                          "figure) and `real_mesh` (the same workload on the FBX-derived 35,440-vertex Y-Bot)")
     ap.add_argument("--dump-lbs-events", default=None, help="write the HIP-event duration of every skin launch of the timed region to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure, each a run of its own outside the timed region: `lbs_alone` (the LBS kernel by "
+                         "itself), `world_sync`, `real_mesh` (both also need no --no-extras) and `cpu_baseline` (also needs no --no-cpu-baseline). "
+                         "Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left to DIR/<name>.npy (float32 / float64, under 64 MB in all): "
+                         "every field of the bodies, controllers, locomotion and action states, and the palettes and skinned positions, normals "
+                         "and tangents of a fixed seeded sample of characters (see _dump_outputs)")
     ap.add_argument("--cpu-sample-chars", type=int, default=2048)
     ap.add_argument("--cpu-sample-steps", type=int, default=16)
     args = ap.parse_args()
@@ -135,8 +145,7 @@ def main():
         else:
             dist.init_process_group(backend=args.dist_backend)
 
-    import __graft_entry__
-    sge = __graft_entry__.build()
+    sge = _load_product()
     abi = sge.abi
 
     # ---- world: replicated per GPU ------------------------------------------------
@@ -200,6 +209,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(eng, args.dump_outputs)  # (before anything below steps or skins the crowd again)
     if args.dump_lbs_events:
         ev = eng.skin_launch_times()
         with open(args.dump_lbs_events, "w") as f:
@@ -220,16 +231,18 @@ def main():
     # settles at 0.86 ms, tools/lbs_sustained.sh). Few launches, so that the rocprofv3 per-kernel average of the whole run stays
     # the timed region's.
     alone_launches = 8
-    eng.synchronize()
-    eng.set_option(abi.OPT_OVERLAP_SKIN, 0)  # by itself means: without the residency cap of the overlap schedule as well
-    eng.profile_read(reset=True)
-    for _ in range(alone_launches):
+    alone = None
+    if args.full:
         eng.synchronize()
-        time.sleep(0.001)
-        eng.tick(dt=0.0, stages=abi.STAGE_SKIN)
-    eng.synchronize()
-    alone = eng.profile_read(reset=True)
-    eng.set_option(abi.OPT_OVERLAP_SKIN, 1 if args.overlap else 0)
+        eng.set_option(abi.OPT_OVERLAP_SKIN, 0)  # by itself means: without the residency cap of the overlap schedule as well
+        eng.profile_read(reset=True)
+        for _ in range(alone_launches):
+            eng.synchronize()
+            time.sleep(0.001)
+            eng.tick(dt=0.0, stages=abi.STAGE_SKIN)
+        eng.synchronize()
+        alone = eng.profile_read(reset=True)
+        eng.set_option(abi.OPT_OVERLAP_SKIN, 1 if args.overlap else 0)
     eng.set_option(abi.OPT_PROFILE, 0)
 
     V, B = eng.vertex_count, eng.bone_count
@@ -242,8 +255,6 @@ def main():
     lbs_bytes = count * (40.0 * V + B * 64.0) + 64.0 * V
     lbs_ms = prof.skin_ms / max(prof.skin_launches, 1)
     achieved = lbs_bytes / (lbs_ms * 1e-3) / 1e9 if lbs_ms > 0 else 0.0
-    alone_ms = alone.skin_ms / max(alone.skin_launches, 1)
-    alone_gbs = lbs_bytes / (alone_ms * 1e-3) / 1e9 if alone_ms > 0 else 0.0
     traffic = _recorded_traffic(count, V, "skin_ticket_multi_kernel" if (_q.value > 0 and _cpw.value > 1) else "skin_ticket_kernel" if _q.value > 0 else "skin_kernel<")
     value = n_total * args.steps / elapsed
     out = {
@@ -279,8 +290,7 @@ def main():
                      "bytes_per_launch": lbs_bytes, "ms_per_launch": lbs_ms,
                      "note": "HIP events on the skin stream over the timed region" + (
                          "; the launches overlap the next step's collision + pose kernels (see lbs_alone for the kernel by itself)" if args.overlap and mode == "ccd" else "")},
-        "lbs_alone": {"ms_per_launch": alone_ms, "achieved": alone_gbs, "frac": alone_gbs / HBM_PEAK_GBS, "unit": "GB/s", "launches": alone_launches,
-                      "note": "the LBS launch of the serial schedule (skin_kernel, one workgroup per character) by itself after the timed region: no other kernel beside it, a 1 ms pause before every launch (back to back it sustains ~0.86 ms: profiles/r2_lbs_sustained_vs_burst.txt)"},
+        **({"lbs_alone": _lbs_alone_record(alone, lbs_bytes, alone_launches)} if alone is not None else {}),  # --full
         "whole_path_hbm_frac": (value / world) * (40.0 * V + 64.0 * V / count + 2 * B * 64.0 + 640.0) / (HBM_PEAK_GBS * 1e9),
         "kernels_ms_per_step": {"move_ccd": prof.move_ms / args.steps, "pose": prof.pose_ms / args.steps,
                                 "lbs": prof.skin_ms / args.steps, "agents_grid": prof.agents_ms / args.steps},
@@ -325,10 +335,10 @@ def main():
                     "self_launched": bool(os.environ.get("SGE_BENCH_SELF_LAUNCHED")), "per_rank": ranks}
     if exchange is not None:
         out["ranks"]["agent_exchange"] = exchange.describe()
-    extras = rank == 0 and world == 1 and not args.no_extras and world_loop is None and exchange is None and not args.refit
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and world_loop is None and exchange is None and not args.refit
     if extras:
         out["world_sync"] = _world_sync_leg(sge, eng, stages, count, elapsed / args.steps * 1e3)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = _cpu_baseline(sge, eng, ybot, terrain, stages & ~abi.STAGE_BLAS_REFIT, args, mode)  # the oracle has no refit
     eng.close()
     if extras and mode == "ccd" and args.mesh == "synthetic" and args.workload == "ccd":
@@ -337,6 +347,62 @@ def main():
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def _load_product():
+    """The package with its HIP library loaded. build() rebuilds what is stale and touches nothing that is current; where the tree
+    cannot be written at all (built by another user, or installed read-only) the library that stands there is loaded as it is:
+    a library that is missing, or that lacks a declared symbol, is still an error, never another code path."""
+    import __graft_entry__
+    try:
+        return __graft_entry__.build()
+    except PermissionError as e:
+        sys.stderr.write("bench.py: the tree cannot be written (%s): loading the library that is built there\n" % e)
+        pkg = importlib.import_module(__graft_entry__.PKG)
+        pkg.abi.load_library()
+        return pkg
+
+
+def _lbs_alone_record(alone, lbs_bytes, launches):
+    alone_ms = alone.skin_ms / max(alone.skin_launches, 1)
+    alone_gbs = lbs_bytes / (alone_ms * 1e-3) / 1e9 if alone_ms > 0 else 0.0
+    return {"ms_per_launch": alone_ms, "achieved": alone_gbs, "frac": alone_gbs / HBM_PEAK_GBS, "unit": "GB/s", "launches": launches,
+            "note": "the LBS launch of the serial schedule (skin_kernel, one workgroup per character) by itself after the timed region: no other kernel beside it, a 1 ms pause before every launch (back to back it sustains ~0.86 ms: profiles/r2_lbs_sustained_vs_burst.txt)"}
+
+
+DUMP_SEED = 4321
+DUMP_SKIN_BYTES = 44e6    # of the sampled characters' skinned streams (40 B per vertex)
+DUMP_STATE_CHARS = 20000  # a crowd larger than this has its state arrays sampled as well (about 0.6 kB per character as float64)
+
+
+def _dump_outputs(eng, out_dir):
+    """What the last timed step left for a caller of the path, as DIR/<name>.npy, under 64 MB in all:
+      <array>_<field>.npy      float64, one per field of the bodies, controllers, locomotion and actions of every character (of
+                               state_characters.npy where the crowd is larger than DUMP_STATE_CHARS)
+      skinned_positions / _normals / _tangents.npy, palettes.npy   float32, of the characters skinned_characters.npy names
+    The samples are drawn from a fixed seed and sorted, so two builds given the same arguments write the same characters."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    eng.synchronize()
+    n, V = eng.count, eng.vertex_count
+    rng = np.random.default_rng(DUMP_SEED)
+    skin_chars = np.sort(rng.choice(n, min(n, max(1, int(DUMP_SKIN_BYTES // (40 * V)))), replace=False))
+    state_chars = np.sort(rng.choice(n, min(n, DUMP_STATE_CHARS), replace=False))
+
+    def save(name, a, dtype):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype))
+
+    state = eng.download(what=("bodies", "controllers", "locomotion", "actions"))
+    for name, arr in state.items():
+        for field in arr.dtype.names:
+            if not field.startswith("_pad"):
+                save("%s_%s" % (name, field), arr[field][state_chars], np.float64)  # (integers and flags are exact in float64)
+    save("state_characters", state_chars, np.float64)
+    skinned = [eng.skinned(first_vertex=int(i) * V, vertex_count=V) for i in skin_chars]
+    for k, name in enumerate(("skinned_positions", "skinned_normals", "skinned_tangents")):
+        save(name, np.stack([s[k] for s in skinned]), np.float32)
+    save("palettes", np.concatenate([eng.palettes(first=int(i), count=1)[0] for i in skin_chars]), np.float32)
+    save("skinned_characters", skin_chars, np.float64)
 
 
 class _WorldLoop:

@@ -239,6 +239,28 @@ def make_fbx_assets():
     for src, dst in (("ExternalResources/17-Cheese.fbx", "cheese_static.npz"),
                      ("ExternalResources/semla/source/Semla.fbx", "semla_static.npz")):
         formats.save_static_payload(os.path.join(OUT, dst), ex.export_static_mesh(fbx.FbxScene(os.path.join(REF, src))))
+    # the skeleton JSON and the FBX limb nodes are the same rig (translations / pre-rotations to print precision); the two FBX files
+    # behind this check and behind cheese_static.npz are too large to be kept as fixtures, so it is made here, where they are read
+    ys = fbx.FbxScene(os.path.join(REF, "ExternalResources/Y Bot.fbx"))
+    sk = json.load(open(os.path.join(REF, "Game/YBot.skeleton.json")))
+    limb = {ys.name(i): i for i in ys.of_kind("Model", "LimbNode")}
+    for k, name in enumerate(sk["names"]):
+        trs = ys.local_trs(limb[name])
+        assert np.abs(trs["T"] - sk["translations"][k]).max() < 1e-6
+        assert np.abs(trs["PreRotation"] - sk["preRotationDegrees"][k]).max() < 1e-6
+
+
+def copy_reference_data():
+    """reference/: the reference's own data files that tests/test_formats.py reads, byte for byte (the 1.8 MB static JSON gzipped)."""
+    import gzip
+    import shutil
+    dst = os.path.join(OUT, "reference")
+    os.makedirs(dst, exist_ok=True)
+    for src in ["Game/YBot.skeleton.json", "ExternalResources/ornate-mirror/source/ornate_mirror.fbx"] + [f"Game/{p}.motionProfile.json" for p in PROFILES]:
+        shutil.copyfile(os.path.join(REF, src), os.path.join(dst, os.path.basename(src)))
+    with open(os.path.join(REF, "Game/ornate_mirror.static.json"), "rb") as f, open(os.path.join(dst, "ornate_mirror.static.json.gz"), "wb") as g:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=g, compresslevel=9, mtime=0) as z:
+            z.write(f.read())
 
 
 def main():
@@ -248,6 +270,7 @@ def main():
     make_static()
     make_pose_chain(load_fit_motion())
     make_fbx_assets()
+    copy_reference_data()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -1,6 +1,7 @@
 """CPU tests of the on-disk format loaders (formats.py), the Blender-free exporters (exporters.py / fbx.py) and the
-FBX-derived fixtures, against the reference's own data where the checkout is present and against the committed
-tables otherwise.  Row f1 of SURVEY.md §8."""
+FBX-derived fixtures, against the reference's own data files (copies under tests/golden/reference/) and against the
+committed tables.  Row f1 of SURVEY.md §8."""
+import gzip
 import json
 import os
 
@@ -9,9 +10,14 @@ import pytest
 
 import oracle_binding as ob
 
-REF = "/root/reference"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
+REF = os.path.join(GOLDEN, "reference")  # data files of the reference, byte for byte (the static JSON gzipped): tests/golden/make_golden.py
+MIRROR_FBX = os.path.join(REF, "ornate_mirror.fbx")
+
+
+def mirror_static_json():
+    with gzip.open(os.path.join(REF, "ornate_mirror.static.json.gz"), "rt") as f:
+        return json.load(f)
 
 
 def skeleton_json(ybot):
@@ -89,34 +95,34 @@ def test_motion_profile_loader_roundtrip(sge, ybot, tmp_path):
     assert F.load_motion_profile(tmp_path / "bad.json", ybot.names) is None
 
 
-@needs_ref
-def test_loaders_on_the_reference_json(sge, ybot):
+def test_loaders_on_the_reference_json(sge, ybot, tmp_path):
     """The committed dense tables are what the loaders produce from the reference's own JSON files."""
     F = sge.formats
-    sk = F.load_skeleton(os.path.join(REF, "Game/YBot.skeleton.json"))
+    sk = F.load_skeleton(os.path.join(REF, "YBot.skeleton.json"))
     assert sk.names == ybot.names
     assert np.array_equal(sk.translations, ybot.translations)
     assert np.array_equal(sk.pre_rotation_degrees, ybot.pre_rotation_degrees)
     assert sk.zero_root == ybot.zero_root and sk.unit_scale == ybot.unit_scale
     for ref in ybot.profiles:
-        p = F.load_motion_profile(os.path.join(REF, "Game/%s.motionProfile.json" % ref["name"]), sk.names)
+        p = F.load_motion_profile(os.path.join(REF, "%s.motionProfile.json" % ref["name"]), sk.names)
         for key in ("bonePresent", "coeffCount", "coeffs"):
             assert np.array_equal(p[key], ref[key])
         assert p["cycleDuration"] == ref["cycleDuration"]
-    parts = F.load_static_mesh(os.path.join(REF, "Game/ornate_mirror.static.json"))
+    path = tmp_path / "ornate_mirror.static.json"
+    path.write_text(json.dumps(mirror_static_json()))
+    parts = F.load_static_mesh(path)
     z = np.load(os.path.join(GOLDEN, "ornate_mirror_static.npz"))
     assert len(parts) == 1 and np.array_equal(parts[0]["positions"], z["positions"])
     assert np.array_equal(parts[0]["indices"], z["indices"]) and len(parts[0]["collisionHulls"]) == 2
     assert np.array_equal(parts[0]["collisionHulls"][1]["positions"], z["hull1.positions"])
 
 
-@needs_ref
 def test_static_exporter_matches_the_reference_exporter_output(sge):
     """Pin: ornate_mirror.fbx through exporters.export_static_mesh == Game/ornate_mirror.static.json
     (Blender + export_static_mesh_json.py): same weld, vertex order, triangulation and matrix_world."""
-    scene = sge.fbx.FbxScene(os.path.join(REF, "ExternalResources/ornate-mirror/source/ornate_mirror.fbx"))
+    scene = sge.fbx.FbxScene(MIRROR_FBX)
     got = sge.exporters.export_static_mesh(scene)["meshes"][0]
-    ref = json.load(open(os.path.join(REF, "Game/ornate_mirror.static.json")))["meshes"][0]
+    ref = mirror_static_json()["meshes"][0]
     assert got["name"] == ref["name"] and got["mesh"]["submeshes"] == ref["mesh"]["submeshes"]
     assert np.array_equal(np.asarray(ref["mesh"]["indices"], np.uint32), got["mesh"]["indices"])
     assert np.array_equal(np.asarray(ref["mesh"]["positions"], np.float64).astype(np.float32), got["mesh"]["positions"])
@@ -124,24 +130,6 @@ def test_static_exporter_matches_the_reference_exporter_output(sge):
     # Blender round-trips custom normals through a 16-bit encoding: direction agrees to that precision
     assert np.abs(np.asarray(ref["mesh"]["normals"]) - got["mesh"]["normals"]).max() < 1e-3
     assert np.abs(np.asarray(ref["transform"]) - got["transform"]).max() < 1e-7
-
-
-@needs_ref
-def test_fbx_fixtures_are_reproducible(sge):
-    F = sge.formats
-    scene = sge.fbx.FbxScene(os.path.join(REF, "ExternalResources/17-Cheese.fbx"))
-    got = sge.exporters.export_static_mesh(scene)["meshes"][0]
-    kept = F.load_payload(os.path.join(GOLDEN, "cheese_static.npz"))["meshes"][0]
-    assert np.array_equal(got["mesh"]["positions"], kept["mesh"]["positions"])
-    assert np.array_equal(got["mesh"]["indices"], kept["mesh"]["indices"])
-    # the skeleton JSON and the FBX limb nodes are the same rig (translations / pre-rotations to print precision)
-    ys = sge.fbx.FbxScene(os.path.join(REF, "ExternalResources/Y Bot.fbx"))
-    sk = json.load(open(os.path.join(REF, "Game/YBot.skeleton.json")))
-    limb = {ys.name(i): i for i in ys.of_kind("Model", "LimbNode")}
-    for k, name in enumerate(sk["names"]):
-        trs = ys.local_trs(limb[name])
-        assert np.abs(trs["T"] - sk["translations"][k]).max() < 1e-6
-        assert np.abs(trs["PreRotation"] - sk["preRotationDegrees"][k]).max() < 1e-6
 
 
 def test_triangulation_rules(sge):
@@ -320,17 +308,15 @@ def test_collision_hulls_of_the_static_exporter(sge):
     assert E.build_collision_hulls(flat, [[0, 1, 2], [1, 2, 3]]) == []
     assert E.convex_hull_part(cube[:3]) is None
     # the one exporter output the reference checkout holds: same parts (same boxes), same budget (reference: 40 and 36 triangles)
-    fbx_path = "/root/reference/ExternalResources/ornate-mirror/source/ornate_mirror.fbx"
-    if os.path.exists(fbx_path):
-        z = np.load(os.path.join(GOLDEN, "ornate_mirror_static.npz"))
-        mesh = E.export_static_mesh(sge.fbx.FbxScene(fbx_path))["meshes"][0]
-        assert len(mesh["collisionHulls"]) == 2
-        for k, h in enumerate(mesh["collisionHulls"]):
-            hp = np.asarray(h["positions"]).reshape(-1, 3)
-            ref = z["hull%d.positions" % k].reshape(-1, 3)
-            assert np.abs(hp.min(0) - ref.min(0)).max() < 2e-3 and np.abs(hp.max(0) - ref.max(0)).max() < 2e-3
-            assert len(h["indices"]) // 3 <= 44
-            assert 0.8 < ConvexHull(hp).volume / ConvexHull(ref).volume < 1.35
+    z = np.load(os.path.join(GOLDEN, "ornate_mirror_static.npz"))
+    mesh = E.export_static_mesh(sge.fbx.FbxScene(MIRROR_FBX))["meshes"][0]
+    assert len(mesh["collisionHulls"]) == 2
+    for k, h in enumerate(mesh["collisionHulls"]):
+        hp = np.asarray(h["positions"]).reshape(-1, 3)
+        ref = z["hull%d.positions" % k].reshape(-1, 3)
+        assert np.abs(hp.min(0) - ref.min(0)).max() < 2e-3 and np.abs(hp.max(0) - ref.max(0)).max() < 2e-3
+        assert len(h["indices"]) // 3 <= 44
+        assert 0.8 < ConvexHull(hp).volume / ConvexHull(ref).volume < 1.35
 
 
 def test_static_loader_semantics(sge, tmp_path):

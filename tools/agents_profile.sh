@@ -4,7 +4,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/r4_agents_prof
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT -o ag --output-format csv -- python3 $REPO/bench.py --steps 100 --warmup 20 --no-extras --no-cpu-baseline --workload agents "$@" > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT -o ag --output-format csv -- python3 $REPO/bench.py --full --steps 100 --warmup 20 --no-extras --no-cpu-baseline --workload agents "$@" > $OUT/bench.json 2> $OUT/bench.err
 python3 - <<PY
 import csv, glob, json
 f = glob.glob("$OUT/**/*kernel_stats.csv", recursive=True)[0]

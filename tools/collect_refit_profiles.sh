@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/refit_profiles
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $REPO/bench.py --refit --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_refit.json 2> $OUT/bench_refit.err
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $REPO/bench.py --full --refit --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_refit.json 2> $OUT/bench_refit.err
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 for mesh in syn real; do
   flag=""; [ $mesh = real ] && flag="--real"

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 for cfg in "serial_two_launches:--refit --no-overlap" "serial_fused:--refit --fuse --no-overlap" "overlap_two_launches:--refit" "overlap_fused:--refit --fuse"; do
   name=${cfg%%:*}; flags=${cfg#*:}
   echo "== $name"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace_$name -o run --output-format csv -- python3 $REPO/bench.py --steps 200 --warmup 20 --no-cpu-baseline $flags > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "$name failed"; tail -n 5 $OUT/bench_$name.err; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace_$name -o run --output-format csv -- python3 $REPO/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline $flags > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "$name failed"; tail -n 5 $OUT/bench_$name.err; exit 1; }
   cp $(find $OUT/trace_$name -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$name.csv
   rm -rf $OUT/trace_$name
 done

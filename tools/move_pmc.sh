@@ -16,7 +16,7 @@ i=0
 for P in "$P1" "$P2" "$P3" "$P4"; do
   i=$((i+1))
   echo "== pass $i: $P"
-  timeout -k 10 400 rocprofv3 --kernel-trace --pmc $P -d $OUT/p$i -o run --output-format csv -- python3 $REPO/bench.py --steps 12 --warmup 3 --no-cpu-baseline "$@" > $OUT/p$i.json 2> $OUT/p$i.err || { echo "pass $i failed"; tail -5 $OUT/p$i.err; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --pmc $P -d $OUT/p$i -o run --output-format csv -- python3 $REPO/bench.py --full --steps 12 --warmup 3 --no-cpu-baseline "$@" > $OUT/p$i.json 2> $OUT/p$i.err || { echo "pass $i failed"; tail -5 $OUT/p$i.err; }
 done
 python3 - $OUT <<'PY'
 import csv, glob, json, os, sys

@@ -2,7 +2,7 @@
 limits resident workgroups per CU) with and without --overlap. Prints one line per configuration."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "10", "--no-cpu-baseline"]
+base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "100", "--warmup", "10", "--no-cpu-baseline"]
 
 
 def run(tag, flags, env):

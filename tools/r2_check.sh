@@ -14,7 +14,7 @@ if [ $rc -ne 0 ]; then echo "GPU tests failed ($rc)"; exit $rc; fi
 for cfg in "default:" "synthetic:--scene synthetic" "lbs:--workload lbs" "merged:--workload mixed" "ybot_cheese:--mesh ybot"; do
   name=${cfg%%:*}; flags=${cfg#*:}
   echo "== bench $name ($flags)"
-  timeout -k 10 400 python bench.py $flags $BENCH_EXTRA > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; exit 1; }
+  timeout -k 10 400 python bench.py --full $flags $BENCH_EXTRA > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; exit 1; }
   python - "$OUT/bench_$name.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

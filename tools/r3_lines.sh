@@ -4,12 +4,12 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/profiles_r3
 mkdir -p $OUT
 cd $REPO
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err
-python3 bench.py > $OUT/bench_default_untraced.json 2> $OUT/bench_default_untraced.err   # the default line (200 steps) without the profiler
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err
+python3 bench.py --full > $OUT/bench_default_untraced.json 2> $OUT/bench_default_untraced.err   # the default line (200 steps) without the profiler
 bash tools/r2_trace.sh profiles_r3/trace_timeline > /dev/null 2>&1
 python3 tools/overlap_timeline.py $(find $OUT/trace_timeline/trace -name "*kernel_trace.csv" | head -1) > $OUT/overlap_timeline.txt 2>&1
 rm -rf $OUT/trace_timeline/trace
-B="python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline"
+B="python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline"
 $B --workload lbs > $OUT/bench_lbs.json 2>/dev/null
 $B --workload mixed > $OUT/bench_merged.json 2>/dev/null
 $B --mesh ybot > $OUT/bench_ybot_cheese.json 2>/dev/null
@@ -17,7 +17,7 @@ $B --scene synthetic > $OUT/bench_synthetic_scene.json 2>/dev/null
 $B --workload agents > $OUT/bench_agents_1gpu.json 2>/dev/null
 $B --mesh ybot --workload mixed --chars 31250 > $OUT/bench_shard_configs3_31250_ybot_mixed.json 2>/dev/null
 $B --workload agents --chars 31250 > $OUT/bench_shard_configs4_31250_agents.json 2>/dev/null
-python3 bench.py --chars 250000 --workload mixed --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_250k_single_gpu.json 2>/dev/null
+python3 bench.py --full --chars 250000 --workload mixed --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_250k_single_gpu.json 2>/dev/null
 for f in $OUT/bench_*.json; do python3 -c "
 import json,sys
 d=json.loads(open('$f').read().strip().splitlines()[-1])

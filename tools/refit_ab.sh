@@ -11,7 +11,7 @@ for i in $(seq 1 $N); do
     lib=$A; [ $v = B ] && lib=$B
     for cfg in "ser_unfused:--refit --no-overlap" "ser_fused:--refit --fuse --no-overlap" "ov_unfused:--refit"; do
       name=${cfg%%:*}; flags=${cfg#*:}
-      SGE_AMD_LIB=$lib timeout -k 10 300 python bench.py $flags --no-cpu-baseline > $OUT/${name}_${v}_$i.json 2> $OUT/${name}_${v}_$i.err || { echo "bench $name $v failed"; tail -n 5 $OUT/${name}_${v}_$i.err; exit 1; }
+      SGE_AMD_LIB=$lib timeout -k 10 300 python bench.py --full $flags --no-cpu-baseline > $OUT/${name}_${v}_$i.json 2> $OUT/${name}_${v}_$i.err || { echo "bench $name $v failed"; tail -n 5 $OUT/${name}_${v}_$i.err; exit 1; }
       python - $OUT/${name}_${v}_$i.json $name $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

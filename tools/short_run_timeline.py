@@ -1,4 +1,4 @@
-"""Reads a rocprofv3 kernel trace of `bench.py --steps 20 --warmup 5` and prints, for the launches around the timed region, every
+"""Reads a rocprofv3 kernel trace of `bench.py --full --steps 20 --warmup 5` and prints, for the launches around the timed region, every
 skin launch (start, duration, idle time on the skin stream in front of it) and the move stage beside it: where a 20-step region
 loses against the steady state (fill, drain, the transient of the first launches after the synchronisation)."""
 import csv, sys

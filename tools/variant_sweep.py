@@ -22,7 +22,7 @@ for lib in libs:
             env[k] = v
     if lib:
         env["SGE_AMD_LIB"] = lib
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "10", "--no-cpu-baseline"] + flags, env=env, capture_output=True, text=True)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "100", "--warmup", "10", "--no-cpu-baseline"] + flags, env=env, capture_output=True, text=True)
     try:
         d = json.loads(p.stdout.strip().splitlines()[-1])
         k = d["kernels_ms_per_step"]
