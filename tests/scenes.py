@@ -153,3 +153,55 @@ def spawn_on_platforms(pkg, eng, ybot, positions):
              "locomotion": pkg.assets.default_locomotion(n, ybot), "actions": pkg.assets.default_actions(n, ybot, present=True)}
     eng.upload(**state)
     return state
+
+
+# ---- random rigs for the pose kernel's generic paths and the skinning forms -----------------------------------------
+
+class _SyntheticRig:
+    """A rig shaped like assets.YBotAssets (same attributes), with a random hierarchy and random Fourier profiles: what the pose
+    kernel's generic paths need that the Y-Bot never shows — bone counts other than 65, orders above 4, translation channels on
+    bones other than the root, a last pass whose bones ARE animated, bones whose parent sits in the same pass."""
+
+    def __init__(self, bones, order, seed, animate_all, translate_some, chain=False):
+        rng = np.random.default_rng(seed)
+        self.names = ["mixamorig:Hips"] + ["bone%03d" % i for i in range(1, bones)]
+        if bones > 12:
+            self.names[5] = "mixamorig:Spine2"
+        self.parent = np.full(bones, -1, np.int32)
+        for i in range(1, bones):
+            self.parent[i] = i - 1 if (chain and i % 3) else int(rng.integers(max(0, i - 9), i))
+        self.translations = rng.uniform(-8, 8, (bones, 3)).astype(np.float32)
+        self.pre_rotation_degrees = rng.uniform(-40, 40, (bones, 3)).astype(np.float32)
+        self.unit_scale = 0.026
+        self.root_fix_degrees = np.array([0, 180, 0], np.float32)
+        self.zero_root = True
+        self.pelvis_index = 0
+        self.lean_index = 5 if bones > 12 else -1
+        self.profile_names = ["Idle", "Walking", "Running", "FallingIdle", "StandingDodgeBackward"]
+        self.profiles = []
+        ncoef = 1 + 2 * order
+        for k, name in enumerate(self.profile_names):
+            present = np.ones(bones, np.uint8) if animate_all else (rng.uniform(size=bones) < 0.8).astype(np.uint8)
+            present[0] = 1
+            count = np.full((bones, 6), 255, np.uint8)
+            coeffs = np.zeros((bones, 6, 17), np.float32)
+            for b in range(bones):
+                if not present[b]:
+                    continue
+                axes = [3, 4, 5] + ([0, 1, 2] if (b == 0 or (translate_some and b % 7 == 3)) else [])
+                for a in axes:
+                    if rng.uniform() < 0.1:
+                        continue                                        # a nil axis
+                    c = ncoef if rng.uniform() < 0.8 else int(rng.integers(0, ncoef + 1))   # ragged and empty rows too
+                    count[b, a] = c
+                    amp = 25.0 if a >= 3 else 3.0
+                    coeffs[b, a, :c] = rng.normal(0, amp, c) / (1 + np.arange(c))
+            self.profiles.append({"name": name, "order": order if k != 1 else max(1, order - 2), "cycleDuration": float(rng.uniform(0.6, 1.6)),
+                                  "sampleFps": 30, "bonePresent": present, "coeffCount": count, "coeffs": coeffs})
+
+    @property
+    def bone_count(self):
+        return len(self.names)
+
+    def profile_index(self, name):
+        return self.profile_names.index(name)

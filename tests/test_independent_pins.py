@@ -18,28 +18,10 @@ import pytest
 
 import oracle_binding as ob
 from scenes import build_scene
+from skin_ref import metal_skinning_f64 as _metal_skinning_f64
 
 
 # ---- (a) skinning -------------------------------------------------------------------------------------------------------
-def _metal_skinning_f64(pos, nrm, tan, idx, w, palette):
-    """skinningKernel, RayTracing.metalinc:758-775. palette: [B][16] column-major float4x4 (palette[b] * float4 = sum_c col_c * v_c)."""
-    M = palette.astype(np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)  # [b][row][col]
-    p4 = np.concatenate([pos, np.ones((len(pos), 1))], 1).astype(np.float64)
-    n4 = np.concatenate([nrm, np.zeros((len(pos), 1))], 1).astype(np.float64)
-    t4 = np.concatenate([tan[:, :3], np.zeros((len(pos), 1))], 1).astype(np.float64)
-    acc, nacc, tacc = (np.zeros((len(pos), 3)) for _ in range(3))
-    for j in range(4):
-        wj = w[:, j].astype(np.float64)
-        use = (wj > 0.0)[:, None]                                        # `if (w.x > 0.0)`
-        Mj = M[idx[:, j]]
-        acc += np.where(use, np.einsum("vrc,vc->vr", Mj, p4)[:, :3] * wj[:, None], 0.0)
-        nacc += np.where(use, np.einsum("vrc,vc->vr", Mj, n4)[:, :3] * wj[:, None], 0.0)
-        tacc += np.where(use, np.einsum("vrc,vc->vr", Mj, t4)[:, :3] * wj[:, None], 0.0)
-    nn = nacc / np.linalg.norm(nacc, axis=1, keepdims=True)
-    tt = tacc / np.linalg.norm(tacc, axis=1, keepdims=True)
-    return acc, nn, np.concatenate([tt, tan[:, 3:4].astype(np.float64)], 1)
-
-
 def test_oracle_skinning_matches_float64_literal_of_the_metal_kernel(sge, ybot):
     cpu = ob.oracle_engine()
     built, asset = sge.crowd.upload_ybot_mesh(cpu, ybot)
