@@ -326,6 +326,29 @@ PROTOTYPES = {
     "sge_blas_profile_read": (C.c_int, [VP, P(C.c_double), P(i64), C.c_int]),
 }
 
+
+# include/sge_amd_variants.h: per-character mesh variants and distance LOD. A table of its own: the product library alone exports
+# these (load_library binds them), PROTOTYPES stays the mirror of include/sge_amd.h.
+SGE_MAX_MESH_VARIANTS = 8
+
+
+class SkinPlanInfo(C.Structure):
+    _fields_ = [("totalVertices", i64), ("capacityVertices", i64), ("perVariant", i32 * SGE_MAX_MESH_VARIANTS),
+                ("units", i32), ("dropped", i32), ("charsPerUnit", i32), ("_pad", i32)]
+
+
+assert C.sizeof(SkinPlanInfo) == 64
+
+VARIANT_PROTOTYPES = {
+    "sge_skinned_mesh_variant_upload": (C.c_int, [VP, i32, P(SkinnedMeshDesc)]),
+    "sge_characters_set_mesh_variants": (C.c_int, [VP, i32, i32, VP]),
+    "sge_crowd_variant_buffer": (C.c_int, [VP, P(VP)]),
+    "sge_lod_select": (C.c_int, [VP, P(f64), P(f32), i32]),
+    "sge_crowd_reserve_vertices": (C.c_int, [VP, i64]),
+    "sge_crowd_vertex_offsets": (C.c_int, [VP, P(VP)]),
+    "sge_skin_plan_read": (C.c_int, [VP, P(SkinPlanInfo)]),
+}
+
 LIB_NAME = "libsge_amd.so"
 
 
@@ -358,7 +381,12 @@ def load_library(path=None):
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    return bind(C.CDLL(path))
+    lib = bind(C.CDLL(path))
+    for name, (res, args) in VARIANT_PROTOTYPES.items():  # (raises AttributeError if one is missing)
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
 
 
 def ptr(a):

@@ -190,6 +190,24 @@ def make_synthetic_skinned_mesh(parent, bind_model, rings=22, segments=10, radiu
     }
 
 
+def decimate_skinned_mesh(mesh, keep):
+    """A cheaper variant of a skinned mesh dict by vertex subsampling: `keep` vertices (an int) or that fraction of them (a float
+    in (0, 1]), evenly spaced over the vertex stream, each with its own normal, tangent, uv, bone indices and weights; triangles
+    whose three corners all survive are kept and renumbered. For tests and demos of the mesh variants (engine.upload_mesh_variant):
+    the bone data stay consistent with the source mesh, the surface is not meant to look like it."""
+    V = mesh["positions"].shape[0]
+    n = int(round(V * keep)) if isinstance(keep, float) else int(keep)
+    n = max(1, min(V, n))
+    pick = np.unique((np.arange(n, dtype=np.int64) * V) // n)
+    out = {k: np.ascontiguousarray(mesh[k][pick]) for k in ("positions", "normals", "tangents", "uvs", "boneIndices", "boneWeights") if k in mesh}
+    if "indices" in mesh:
+        remap = np.full(V, -1, np.int64)
+        remap[pick] = np.arange(pick.shape[0])
+        tri = remap[np.asarray(mesh["indices"], np.int64).reshape(-1, 3)]
+        out["indices"] = np.ascontiguousarray(tri[(tri >= 0).all(1)].reshape(-1), np.uint32)
+    return out
+
+
 # --------------------------------------------------------------------------- #
 # synthetic static mesh                                                        #
 # --------------------------------------------------------------------------- #

@@ -116,6 +116,19 @@ struct sge_context {
     DevBuf dBodies, dParams, dCtrl, dIntents, dLoco, dActions, dPalettes[2], dPoseModel, dPoseLocal, dMoveScratch, dPoseIn[2];
     DevBuf dOutPos, dOutNrm, dOutTan;
     int outLayoutAllocated = -1;
+    // mesh variants (include/sge_amd_variants.h): meshes 1.. beside `mesh` (variant 0), a variant byte per character, and what the
+    // plan kernel in front of every skin launch writes. extraVariants == 0: none of this is touched by sge_tick.
+    int extraVariants = 0;
+    DevMesh variantMesh[SGE_MAX_MESH_VARIANTS] = {};
+    DevBuf dVarPos[SGE_MAX_MESH_VARIANTS], dVarNrm[SGE_MAX_MESH_VARIANTS], dVarTan[SGE_MAX_MESH_VARIANTS], dVarIdx[SGE_MAX_MESH_VARIANTS], dVarWgt[SGE_MAX_MESH_VARIANTS];
+    DevBuf dVariantTable, dVariantOf, dVariantSnap[2], dVertexOff, dVariantLists, dSkinPlan;
+    long long reservedVertices = 0; // sge_crowd_reserve_vertices; 0 = count x the largest uploaded vertexCount
+    // the skin stage copies the variant bytes on the main stream when the tick is issued (slot = palRead) and the plan kernel reads
+    // the copy on the skin stream: evVariantSnap orders the plan behind the copy, evPlanDone[slot] the next copy behind the plan
+    hipEvent_t evVariantSnap = nullptr, evPlanDone[2] = {nullptr, nullptr};
+    bool planPending[2] = {false, false}, planValid = false;
+    struct VariantStage { uint8_t* host = nullptr; size_t bytes = 0; hipEvent_t copied = nullptr; bool inFlight = false; } variantStage[2];
+    int variantStageSlot = 0;
     // agents
     DevAgents agents{};
     DevBuf dCellStart, dCellItems, dCellCursor, dAgentMinMax, dAgentGrid, dAgentsAll;
@@ -201,6 +214,8 @@ int syncAll(sge_context* c) {
     if (c->copyStream) SGE_HIP(hipStreamSynchronize(c->copyStream));
     c->skinPending[0] = c->skinPending[1] = false;
     c->posePending[0] = c->posePending[1] = false;
+    c->planPending[0] = c->planPending[1] = false;
+    c->variantStage[0].inFlight = c->variantStage[1].inFlight = false;
     return SGE_OK;
 }
 // The main stream must not touch what the animation stages own (locomotion / action states, transformRotation, palettes) while a
@@ -282,6 +297,33 @@ int rebuildPoseSlots(sge_context* c) {
     return SGE_OK;
 }
 
+int variantsUploaded(const sge_context* c) { return c->mesh.vertexCount > 0 ? 1 + c->extraVariants : 0; }
+// capacity of the three output streams in vertices: the reservation, or every character in the largest uploaded mesh
+size_t outputCapacity(const sge_context* c) {
+    // (a reservation holds only beside variants: the uniform launch forms write count x vertexCount whatever is reserved)
+    if (c->reservedVertices > 0 && c->extraVariants > 0) return (size_t)c->reservedVertices;
+    int largest = c->mesh.vertexCount;
+    for (int v = 1; v <= c->extraVariants; ++v) largest = std::max(largest, c->variantMesh[v].vertexCount);
+    return (size_t)c->crowd.count * (size_t)largest;
+}
+// The device table of the uploaded meshes; a variant's vertex splits are fixed here (launch_skin's rule over the crowd's groups).
+// Callers have synchronised.
+int refreshVariantTable(sge_context* c) {
+    if (c->extraVariants == 0) return SGE_OK;
+    DevVariant rows[SGE_MAX_MESH_VARIANTS] = {};
+    const int cpw = variantCharsPerUnit(c->boneCount, c->residentSkinCharsPerUnit);
+    const int groups = std::max(1, (c->crowd.count + cpw - 1) / cpw);
+    c->variantMesh[0] = c->mesh;
+    for (int v = 0; v <= c->extraVariants; ++v) {
+        rows[v].mesh = c->variantMesh[v];
+        variantSplits(rows[v].mesh.vertexCount, groups, rows[v].splits, rows[v].vertsPerSplit);
+    }
+    int rc = upload(c->dVariantTable, rows, sizeof(rows), c->stream);
+    if (rc != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    return SGE_OK;
+}
+
 // The three skinned output streams are the path's HBM traffic (40 B per vertex per step). On MI355X the rate of the three-stream
 // store pattern depends on where the driver placed the buffers: 0.81 or 1.05-1.10 ms for 5.63 GB, bimodal and reproducible per
 // allocation. What decides is the placement of ONE stream — in every exchange of single buffers between a fast and a slow set the
@@ -291,7 +333,8 @@ int rebuildPoseSlots(sge_context* c) {
 // allocated (and held, so that they land in different places) and timed in the real three-stream pattern with the other two fixed.
 // A candidate costs 16 (or 12) bytes per vertex instead of 40: a crowd that fills half the memory can still be probed.
 int allocCrowdOutputs(sge_context* c) {
-    const size_t verts = (size_t)c->crowd.count * (size_t)c->mesh.vertexCount;
+    const size_t verts = outputCapacity(c); // count x vertexCount unless variants or a reservation say otherwise
+    const int probeVerts = c->crowd.count > 0 ? (int)std::min<size_t>(verts / (size_t)c->crowd.count, (size_t)1 << 30) : 0; // the probes' vertices per workgroup
     const size_t stride = c->skinLayout == SGE_LAYOUT_PADDED16 ? 16 : 12;
     const size_t need[3] = {verts * stride, verts * stride, verts * 16};
     DevBuf* bufs[3] = {&c->dOutPos, &c->dOutNrm, &c->dOutTan};
@@ -310,9 +353,9 @@ int allocCrowdOutputs(sge_context* c) {
     SGE_HIP(hipEventCreate(&e1));
     void* cur[3] = {bufs[0]->p, bufs[1]->p, bufs[2]->p};
     auto probe = [&](void* const p[3], float& ms) -> int {
-        launch_store_probe(p[0], p[1], p[2], c->crowd.count, c->mesh.vertexCount, c->skinLayout, c->stream); // warm: first touch
+        launch_store_probe(p[0], p[1], p[2], c->crowd.count, probeVerts, c->skinLayout, c->stream); // warm: first touch
         SGE_HIP(hipEventRecord(e0, c->stream));
-        for (int r = 0; r < 2; ++r) launch_store_probe(p[0], p[1], p[2], c->crowd.count, c->mesh.vertexCount, c->skinLayout, c->stream);
+        for (int r = 0; r < 2; ++r) launch_store_probe(p[0], p[1], p[2], c->crowd.count, probeVerts, c->skinLayout, c->stream);
         SGE_HIP(hipEventRecord(e1, c->stream));
         SGE_HIP(hipEventSynchronize(e1));
         SGE_HIP(hipEventElapsedTime(&ms, e0, e1));
@@ -644,6 +687,11 @@ void sge_context_destroy(sge_context* c) {
                       &c->dBlasRoundLen, &c->dBlasRoundCluster, &c->dBlasRoundIds, &c->dBlasWorldBoxes, &c->dBlasUVs, &c->dBlasQueue, &c->dSkinQueue,
                       &c->dBlasInstPoints, &c->dBlasInstMinMax, &c->dBlasInstGrid, &c->dBlasInstOrder, &c->dBlasGroupBoxes};
     for (DevBuf* b : bufs) b->release();
+    for (int v = 0; v < SGE_MAX_MESH_VARIANTS; ++v)
+        for (DevBuf* b : {&c->dVarPos[v], &c->dVarNrm[v], &c->dVarTan[v], &c->dVarIdx[v], &c->dVarWgt[v]}) b->release();
+    for (DevBuf* b : {&c->dVariantTable, &c->dVariantOf, &c->dVariantSnap[0], &c->dVariantSnap[1], &c->dVertexOff, &c->dVariantLists, &c->dSkinPlan}) b->release();
+    for (hipEvent_t e : {c->evVariantSnap, c->evPlanDone[0], c->evPlanDone[1], c->variantStage[0].copied, c->variantStage[1].copied}) if (e) (void)hipEventDestroy(e);
+    for (auto& st : c->variantStage) if (st.host) (void)hipHostFree(st.host);
     for (int k = 0; k < 2; ++k) {
         c->pull[k].stage.release();
         if (c->pull[k].host) (void)hipHostFree(c->pull[k].host);
@@ -883,7 +931,127 @@ int sge_skinned_mesh_upload(sge_context* c, const sge_skinned_mesh_desc* d) {
     c->hostBlas = HostBlas{}; // a new mesh invalidates the acceleration structure built for the old one
     c->blas = DevBlas{};
     c->blasHasUVs = false;
+    if ((rc = refreshVariantTable(c)) != SGE_OK) return rc;
     if (c->crowd.count > 0) return allocCrowdOutputs(c);
+    return SGE_OK;
+}
+
+int sge_skinned_mesh_variant_upload(sge_context* c, int32_t variant, const sge_skinned_mesh_desc* d) {
+    if (c) { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    if (!c || !d || d->vertexCount <= 0 || !d->positions || !d->normals || !d->tangents || !d->boneIndices || !d->boneWeights) {
+        set_error("sge_skinned_mesh_variant_upload: bad argument");
+        return SGE_ERR_INVALID;
+    }
+    if (c->mesh.vertexCount == 0) { set_error("sge_skinned_mesh_variant_upload needs sge_skinned_mesh_upload (variant 0) first"); return SGE_ERR_STATE; }
+    if (variant <= 0 || variant >= SGE_MAX_MESH_VARIANTS) { set_error("variant index out of range (variant 0 is replaced through sge_skinned_mesh_upload)"); return SGE_ERR_INVALID; }
+    if (variant > c->extraVariants + 1) { set_error("variants are numbered without gaps: upload the next free index"); return SGE_ERR_INVALID; }
+    if (d->invBindModel) { set_error("a variant shares variant 0's inverse bind matrices: invBindModel must be NULL"); return SGE_ERR_INVALID; }
+    const size_t V = (size_t)d->vertexCount;
+    for (size_t i = 0; i < V * 4; ++i)
+        if (d->boneIndices[i] >= c->boneCount) { set_error("bone index out of range"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    int rc;
+    hipStream_t s = c->stream;
+    if (!c->evVariantSnap) {
+        SGE_HIP(hipEventCreateWithFlags(&c->evVariantSnap, hipEventDisableTiming));
+        SGE_HIP(hipEventCreateWithFlags(&c->evPlanDone[0], hipEventDisableTiming));
+        SGE_HIP(hipEventCreateWithFlags(&c->evPlanDone[1], hipEventDisableTiming));
+    }
+    if ((rc = upload(c->dVarPos[variant], d->positions, V * 12, s)) != SGE_OK) return rc;
+    if ((rc = upload(c->dVarNrm[variant], d->normals, V * 12, s)) != SGE_OK) return rc;
+    if ((rc = upload(c->dVarTan[variant], d->tangents, V * 16, s)) != SGE_OK) return rc;
+    if ((rc = upload(c->dVarIdx[variant], d->boneIndices, V * 8, s)) != SGE_OK) return rc;
+    if ((rc = upload(c->dVarWgt[variant], d->boneWeights, V * 16, s)) != SGE_OK) return rc;
+    if ((rc = c->dSkinPlan.alloc(sizeof(SkinPlan))) != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(s));
+    c->variantMesh[variant] = DevMesh{d->vertexCount, c->dVarPos[variant].as<float>(), c->dVarNrm[variant].as<float>(), c->dVarTan[variant].as<float>(),
+                                      c->dVarIdx[variant].as<uint16_t>(), c->dVarWgt[variant].as<float>()};
+    c->extraVariants = std::max(c->extraVariants, (int)variant);
+    c->planValid = false;
+    if ((rc = refreshVariantTable(c)) != SGE_OK) return rc;
+    if (c->crowd.count > 0) return allocCrowdOutputs(c);
+    return SGE_OK;
+}
+
+int sge_characters_set_mesh_variants(sge_context* c, int32_t first, int32_t count, const uint8_t* variants) {
+    if (!c || first < 0 || count < 0 || first + count > c->crowd.count || (count > 0 && !variants)) { set_error("sge_characters_set_mesh_variants: bad argument"); return SGE_ERR_INVALID; }
+    const int known = std::max(1, variantsUploaded(c));
+    for (int i = 0; i < count; ++i)
+        if (variants[i] >= known) { set_error("mesh variant was never uploaded"); return SGE_ERR_INVALID; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    // through pinned staging, two slots: the caller's array is free when the call returns and the copy stays asynchronous
+    sge_context::VariantStage& S = c->variantStage[c->variantStageSlot];
+    if (!S.copied) SGE_HIP(hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
+    if (S.inFlight) { SGE_HIP(hipEventSynchronize(S.copied)); S.inFlight = false; }
+    if (S.bytes < (size_t)count) {
+        if (S.host) (void)hipHostFree(S.host);
+        S.host = nullptr; S.bytes = 0;
+        SGE_HIP(hipHostMalloc(reinterpret_cast<void**>(&S.host), (size_t)c->crowd.count, hipHostMallocDefault));
+        S.bytes = (size_t)c->crowd.count;
+    }
+    memcpy(S.host, variants, (size_t)count);
+    SGE_HIP(hipMemcpyAsync(c->dVariantOf.as<uint8_t>() + first, S.host, (size_t)count, hipMemcpyHostToDevice, c->stream));
+    SGE_HIP(hipEventRecord(S.copied, c->stream));
+    S.inFlight = true;
+    c->variantStageSlot ^= 1;
+    return SGE_OK;
+}
+
+int sge_crowd_variant_buffer(sge_context* c, void** d_variants) {
+    if (!c || !d_variants) return SGE_ERR_INVALID;
+    if (c->crowd.count == 0) { set_error("no characters"); return SGE_ERR_STATE; }
+    *d_variants = c->dVariantOf.p;
+    return SGE_OK;
+}
+
+int sge_lod_select(sge_context* c, const double eye[3], const float* distances, int32_t n) {
+    if (!c || !eye || n < 0 || n > SGE_MAX_MESH_VARIANTS - 1 || (n > 0 && !distances)) { set_error("sge_lod_select: bad argument"); return SGE_ERR_INVALID; }
+    for (int i = 0; i < n; ++i)
+        if (!(distances[i] >= 0.0f) || (i > 0 && !(distances[i] > distances[i - 1]))) { set_error("sge_lod_select: distances must be >= 0 and strictly ascending"); return SGE_ERR_INVALID; }
+    if (c->crowd.count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    // positions of the newest move stage: its launches are all on, or joined into, the main stream (launch_move)
+    launch_lod_select(c->dBodies.as<sge_body_state>(), c->crowd.count, eye, distances, n, std::max(1, variantsUploaded(c)) - 1,
+                      c->dVariantOf.as<uint8_t>(), c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+
+int sge_crowd_reserve_vertices(sge_context* c, int64_t vertices) {
+    if (!c || vertices < 0 || (vertices > 0 && vertices < c->crowd.count)) { set_error("sge_crowd_reserve_vertices: fewer vertices than characters"); return SGE_ERR_INVALID; }
+    // only the plan kernel of the variant path cuts at a capacity; a uniform crowd writes count x vertexCount vertices
+    if (vertices > 0 && c->extraVariants == 0) { set_error("sge_crowd_reserve_vertices needs a mesh variant >= 1 (sge_skinned_mesh_variant_upload): the uniform layout is count x vertexCount"); return SGE_ERR_STATE; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    c->reservedVertices = vertices;
+    if (c->mesh.vertexCount > 0 && c->crowd.count > 0) return allocCrowdOutputs(c);
+    return SGE_OK;
+}
+
+int sge_crowd_vertex_offsets(sge_context* c, void** d_offsets) {
+    if (!c || !d_offsets) return SGE_ERR_INVALID;
+    if (c->extraVariants == 0) { set_error("no mesh variant uploaded: character c starts at vertex c x vertexCount"); return SGE_ERR_STATE; }
+    if (c->crowd.count == 0) { set_error("no characters"); return SGE_ERR_STATE; }
+    *d_offsets = c->dVertexOff.p;
+    return SGE_OK;
+}
+
+int sge_skin_plan_read(sge_context* c, sge_skin_plan_info* out) {
+    if (!c || !out) return SGE_ERR_INVALID;
+    if (!c->planValid) { set_error("no skin stage with mesh variants has run"); return SGE_ERR_STATE; }
+    (void)hipSetDevice(c->device);
+    { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; } // a launch on the skin stream is joined into the main stream, a serial one is on it
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    SkinPlan P;
+    SGE_HIP(hipMemcpy(&P, c->dSkinPlan.p, sizeof(P), hipMemcpyDeviceToHost));
+    *out = sge_skin_plan_info{};
+    out->totalVertices = P.totalVertices;
+    out->capacityVertices = P.capacityVertices;
+    for (int v = 0; v < SGE_MAX_MESH_VARIANTS; ++v) out->perVariant[v] = P.kept[v];
+    out->units = P.units;
+    out->dropped = P.dropped;
+    out->charsPerUnit = P.charsPerUnit;
     return SGE_OK;
 }
 
@@ -1300,12 +1468,21 @@ int sge_characters_resize(sge_context* c, int32_t count) {
     SGE_ZALLOC(c->dListCounts, 4 * sizeof(int));
     SGE_ZALLOC(c->dOrderHist, 64 * sizeof(int));
     if (c->storePoseDebug) { SGE_ZALLOC(c->dPoseModel, N * B * 64); SGE_ZALLOC(c->dPoseLocal, N * B * 64); }
+    // mesh variants: every character starts in variant 0; a reservation made for another crowd size is dropped
+    SGE_ZALLOC(c->dVariantOf, N);
+    SGE_ZALLOC(c->dVariantSnap[0], N);
+    SGE_ZALLOC(c->dVariantSnap[1], N);
+    SGE_ZALLOC(c->dVertexOff, (N + 1) * sizeof(long long));
+    SGE_ZALLOC(c->dVariantLists, N * sizeof(int));
+    c->reservedVertices = 0;
+    c->planValid = false;
 #undef SGE_ZALLOC
     c->crowd = DevCrowd{count, c->dBodies.as<sge_body_state>(), c->dParams.as<sge_controller_params>(),
                         c->dCtrl.as<sge_controller_state>(), c->dIntents.as<sge_move_intent>(),
                         c->dLoco.as<sge_locomotion_state>(), c->dActions.as<sge_action_state>(), c->dPalettes[0].as<float>(),
                         c->storePoseDebug ? c->dPoseModel.as<float>() : nullptr, c->storePoseDebug ? c->dPoseLocal.as<float>() : nullptr,
                         nullptr};
+    if ((rc = refreshVariantTable(c)) != SGE_OK) return rc;
     if (c->mesh.vertexCount > 0 && (rc = allocCrowdOutputs(c)) != SGE_OK) return rc;
     if ((rc = ensureBlasBuffers(c)) != SGE_OK) return rc;
     SGE_HIP(hipStreamSynchronize(c->stream));
@@ -1370,7 +1547,7 @@ int sge_palettes_download(sge_context* c, int32_t first, int32_t count, float* p
 
 int sge_skinned_download(sge_context* c, int64_t first_vertex, int64_t vertex_count, float* positions, float* normals, float* tangents) {
     if (!c || first_vertex < 0 || vertex_count < 0 ||
-        (size_t)(first_vertex + vertex_count) > (size_t)c->crowd.count * (size_t)c->mesh.vertexCount) { set_error("vertex range out of bounds"); return SGE_ERR_INVALID; }
+        (size_t)(first_vertex + vertex_count) > outputCapacity(c)) { set_error("vertex range out of bounds"); return SGE_ERR_INVALID; }
     (void)hipSetDevice(c->device);
     const bool padded = c->outLayoutAllocated == SGE_LAYOUT_PADDED16;
     const size_t n = (size_t)vertex_count, f = (size_t)first_vertex;
@@ -1584,6 +1761,10 @@ int sge_tick(sge_context* c, const sge_tick_desc* d) {
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
     const uint32_t st = d->stages;
+    if (c->extraVariants > 0) { // include/sge_amd_variants.h, "Out of scope"
+        if (st & SGE_STAGE_BLAS_REFIT) { set_error("SGE_STAGE_BLAS_REFIT is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
+        if ((st & SGE_STAGE_SKIN) && (first != 0 || count != c->crowd.count)) { set_error("SGE_STAGE_SKIN works on the whole crowd while mesh variants are uploaded (first = 0, count = all): the vertex offsets are a scan over every character"); return SGE_ERR_STATE; }
+    }
     // Overlap mode, a whole-crowd tick with move + pose + skin: the pose launch goes to the pose stream and reads the move stage's
     // results from the copy the move kernels write (PoseInput), so that the NEXT tick's move stage does not queue behind it.
     // (not with the separation stage, which moves bodies after the move kernels have written the copy)
@@ -1723,6 +1904,19 @@ int sge_tick(sge_context* c, const sge_tick_desc* d) {
                      (long long)first * c->mesh.vertexCount, SGE_LAYOUT_PACKED, c->skinLayout, c->dOutPos.p, c->dOutNrm.p, c->dOutTan.p};
         hipStream_t ss = c->stream;
         const bool overlap = c->overlapSkin;
+        const bool variants = c->extraVariants > 0;
+        const int planSlot = c->palRead;
+        if (variants) {
+            // the variant bytes as they stand HERE in the main stream's order are this launch's: copied to the slot no plan kernel
+            // newer than plan(n-2) reads, so that a later sge_characters_set_mesh_variants / sge_lod_select never changes them under
+            // the launch (which, in overlap mode, starts later on the skin stream)
+            if (c->planPending[planSlot]) { SGE_HIP(hipStreamWaitEvent(c->stream, c->evPlanDone[planSlot], 0)); c->planPending[planSlot] = false; }
+            SGE_HIP(hipMemcpyAsync(c->dVariantSnap[planSlot].p, c->dVariantOf.p, (size_t)c->crowd.count, hipMemcpyDeviceToDevice, c->stream));
+            if (overlap) {
+                SGE_HIP(hipEventRecord(c->evVariantSnap, c->stream));
+                SGE_HIP(hipStreamWaitEvent(c->skinStream, c->evVariantSnap, 0));
+            }
+        }
         if (overlap) {
             // skin(n) on its own stream after pose(n) (and, stream order, after skin(n-1)); move(n+1) and pose(n+1) may run on
             // the main stream meanwhile
@@ -1751,7 +1945,22 @@ int sge_tick(sge_context* c, const sge_tick_desc* d) {
                 int quarters = 0;
                 if (overlap && c->residentSkinQuarters >= 0) quarters = c->residentSkinQuarters;
                 else if (overlap && count >= kResidentSkinCharacters) quarters = (st & SGE_STAGE_AGENTS) ? kResidentSkinQuartersWithAgents : kResidentSkinQuarters;
-                const int form = launch_skin(L, ss, overlap ? c->overlapSkinWorkgroups : 0, c->dSkinQueue.as<int>(), quarters, c->residentSkinCharsPerUnit);
+                int form;
+                if (variants) {
+                    // plan + skin_variant_kernel: always resident; where the uniform path would take workgroups that come and go
+                    // (small crowds, no overlap) as many as the registers let stay (five per CU)
+                    if (quarters <= 0) quarters = 20;
+                    VariantSkinLaunch VL{c->dVariantTable.as<DevVariant>(), 1 + c->extraVariants, c->dVariantSnap[planSlot].as<uint8_t>(),
+                                         c->dVertexOff.as<long long>(), c->dVariantLists.as<int>(), c->dSkinPlan.as<SkinPlan>(),
+                                         c->crowd.palettes, c->boneCount, count, (long long)outputCapacity(c), c->skinLayout,
+                                         c->dOutPos.p, c->dOutNrm.p, c->dOutTan.p};
+                    form = launch_skin_variants(VL, ss, c->dSkinQueue.as<int>(), quarters, c->residentSkinCharsPerUnit, overlap ? c->evPlanDone[planSlot] : nullptr);
+                    if (form <= 0) { set_error("the skin launch over mesh variants could not be set up"); return SGE_ERR_STATE; }
+                    if (overlap) c->planPending[planSlot] = true;
+                    c->planValid = true;
+                } else {
+                    form = launch_skin(L, ss, overlap ? c->overlapSkinWorkgroups : 0, c->dSkinQueue.as<int>(), quarters, c->residentSkinCharsPerUnit);
+                }
                 SGE_HIP(hipGetLastError()); // a launch that could not start would leave the previous frame's streams in place
                 c->lastSkinQuarters = form > 0 ? quarters : 0; // what ran, not what was asked for (sge_debug_skin_form)
                 c->lastSkinCharsPerUnit = form > 0 ? form : 1;
@@ -1831,6 +2040,7 @@ int sge_blas_info_get(sge_context* c, sge_blas_info* info) {
 
 int sge_blas_refit(sge_context* c, int32_t first, int32_t count) {
     SGE_RANGE_CHECK();
+    if (c->extraVariants > 0) { set_error("sge_blas_refit is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
     if (c->blas.entryCount == 0) { set_error("sge_blas_refit needs sge_blas_build"); return SGE_ERR_STATE; }
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
@@ -1848,6 +2058,7 @@ int sge_blas_refit_buffers(sge_context* c, const void* d_positions, int32_t layo
         set_error("sge_blas_refit_buffers: bad argument");
         return SGE_ERR_INVALID;
     }
+    if (c->extraVariants > 0) { set_error("sge_blas_refit_buffers is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
     if (c->blas.entryCount == 0) { set_error("sge_blas_refit_buffers needs sge_blas_build"); return SGE_ERR_STATE; }
     (void)hipSetDevice(c->device);
     { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
@@ -1888,6 +2099,7 @@ int sge_blas_instances_upload(sge_context* c, int32_t first, int32_t count, cons
 
 int sge_blas_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t count, sge_blas_hit* hits) {
     if (!c || count < 0 || (count > 0 && (!rays || !hits))) { set_error("sge_blas_intersect_batch: bad argument"); return SGE_ERR_INVALID; }
+    if (c->extraVariants > 0) { set_error("sge_blas_intersect_batch is not available while mesh variants are uploaded: the boxes and the index buffer are variant 0's, the streams are ragged"); return SGE_ERR_STATE; }
     if (c->blas.entryCount == 0 || c->crowd.count == 0) { set_error("sge_blas_intersect_batch needs sge_blas_build and characters"); return SGE_ERR_STATE; }
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
@@ -1910,6 +2122,7 @@ int sge_blas_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t c
 
 int sge_blas_intersect_device(sge_context* c, const void* d_rays, int32_t count, void* d_hits, int32_t any_instance) {
     if (!c || count < 0 || (count > 0 && (!d_rays || !d_hits))) { set_error("sge_blas_intersect_device: bad argument"); return SGE_ERR_INVALID; }
+    if (c->extraVariants > 0) { set_error("sge_blas_intersect_device is not available while mesh variants are uploaded: the boxes and the index buffer are variant 0's, the streams are ragged"); return SGE_ERR_STATE; }
     if (c->blas.entryCount == 0 || c->crowd.count == 0) { set_error("sge_blas_intersect_device needs sge_blas_build and characters"); return SGE_ERR_STATE; }
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);

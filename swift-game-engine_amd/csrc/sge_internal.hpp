@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "../../include/sge_amd.h"
+#include "../../include/sge_amd_variants.h"
 #include "sge_math.hpp"
 
 namespace sge {
@@ -21,6 +22,7 @@ static_assert(sizeof(sge_capsule_cast_hit) == 60, "layout");
 static_assert(sizeof(sge_capsule_overlap_hit) == 56, "layout");
 static_assert(sizeof(sge_bvh_node) == 44, "layout");
 static_assert(sizeof(sge_tick_desc) == 32, "layout");
+static_assert(sizeof(sge_skin_plan_info) == 64, "layout");
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
@@ -345,6 +347,42 @@ struct SkinJobDev {
 void launch_skin_jobs(const SkinJobDev* d_jobs, const int2* d_blockJob, int blocks, int vertsPerBlock, int dstLayout,
                       void* outPos, void* outNrm, void* outTan, hipStream_t s);
 void launch_store_probe(void* outPos, void* outNrm, void* outTan, int chars, int vertexCount, int dstLayout, hipStream_t s);
+
+// ---- mesh variants (include/sge_amd_variants.h, sge_skin_variants.hip) ---- //
+// One row per uploaded mesh, in device memory (the kernels index the table with a value decoded on the device).
+struct DevVariant {
+    DevMesh mesh;
+    int splits, vertsPerSplit; // the variant's vertex range is cut into `splits` pieces of vertsPerSplit (a multiple of kSkinBlock) vertices
+};
+// What the plan kernel leaves for the skin launch behind it (and for sge_skin_plan_read). Unused variants carry
+// listBase = kept characters, unitBase = units, so that a search over the bases never lands on them.
+struct SkinPlan {
+    long long totalVertices, capacityVertices;
+    int kept[SGE_MAX_MESH_VARIANTS];          // characters of every variant's list
+    int listBase[SGE_MAX_MESH_VARIANTS + 1];  // exclusive scan of kept
+    int unitBase[SGE_MAX_MESH_VARIANTS + 1];  // first work unit of every variant; [variants] = units
+    int units, dropped, charsPerUnit, variants;
+};
+struct VariantSkinLaunch {
+    const DevVariant* table; int variants;     // uploaded rows
+    const uint8_t* variantOf;                  // [chars] (the tick's copy of the array)
+    long long* off;                            // [chars + 1]
+    int* lists;                                // [chars] character indices grouped by variant
+    SkinPlan* plan;
+    const float* palettes; int paletteCount, chars;
+    long long capacityVertices;
+    int dstLayout;
+    void* outPos; void* outNrm; void* outTan;
+};
+// plan kernel + skin_variant_kernel on `s`; quarters of a resident workgroup per CU; planDone (or null) is recorded behind the plan kernel;
+// returns the characters per unit it took (0: error)
+int launch_skin_variants(const VariantSkinLaunch& L, hipStream_t s, int* residentQueue, int residentQuarters, int charsPerUnit, hipEvent_t planDone);
+// characters per unit the variant launch takes for a rig of paletteCount bones when `charsPerUnit` is asked for
+int variantCharsPerUnit(int paletteCount, int charsPerUnit);
+// vertex splits of a variant of `vertexCount` vertices in a crowd of `groups` groups (launch_skin's rule)
+void variantSplits(int vertexCount, int groups, int& splits, int& vertsPerSplit);
+void launch_lod_select(const sge_body_state* bodies, int count, const double eye[3], const float* distances, int n, int highestVariant,
+                       uint8_t* variantOf, hipStream_t s);
 
 void launch_agents_export(const DevCrowd& crowd, sge_agent_state* d_out, hipStream_t s);
 void launch_agents_pad(sge_agent_state* d_out, int n, hipStream_t s);

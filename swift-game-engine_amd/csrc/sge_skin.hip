@@ -14,6 +14,9 @@
 // This translation unit is compiled with the default -ffp-contract=fast: the Metal
 // original is built with MTL_FAST_MATH (project.pbxproj:328,386), there are no
 // thresholds downstream of this arithmetic, and the parity bound is 1e-5 relative.
+// sge_skin_vertex.hpp holds a twin of VertexIn, loadVertex, the palette staging and the per-vertex arithmetic of skinRange /
+// skinRangeMulti for sge_skin_variants.hip (why a twin: see that header). A change to the arithmetic here has to be made there
+// as well; tests/test_gpu_mesh_variants.py compares the two bit for bit on the GPU.
 #include <algorithm>
 #include "sge_blas_dev.hpp"
 

@@ -17,6 +17,18 @@ class SgeError(RuntimeError):
     pass
 
 
+_HIP = None
+
+
+def _hip_runtime():
+    """The HIP runtime the product library is linked against, opened once (vertex_offsets copies a device array the C ABI hands out)."""
+    global _HIP
+    if _HIP is None:
+        _HIP = C.CDLL("libamdhip64.so")
+        _HIP.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return _HIP
+
+
 class _ProductTable:
     """sge_* entry points of the HIP library."""
 
@@ -160,6 +172,63 @@ class CharacterEngine:
         self.vertex_count = V
         self.mesh = dict(mesh, **keep)
         return self.mesh
+
+    # -- mesh variants and distance LOD (include/sge_amd_variants.h; product only) -- #
+    def upload_mesh_variant(self, variant, mesh):
+        """Mesh number `variant` (1..7) beside the mesh of upload_skinned_mesh (variant 0): same skeleton, variant 0's inverse binds."""
+        if "tangents" not in mesh:
+            mesh = dict(mesh, tangents=self.compute_tangents(mesh["positions"], mesh["normals"], mesh["uvs"], mesh["indices"]))
+        d = abi.SkinnedMeshDesc()
+        V = mesh["positions"].shape[0]
+        d.vertexCount = V
+        keep = {k: np.ascontiguousarray(mesh[k], np.float32) for k in ("positions", "normals", "tangents", "boneWeights")}
+        keep["boneIndices"] = np.ascontiguousarray(mesh["boneIndices"], np.uint16)
+        for k in ("positions", "normals", "tangents", "boneWeights"):
+            setattr(d, k, keep[k].ctypes.data_as(C.POINTER(C.c_float)))
+        d.boneIndices = keep["boneIndices"].ctypes.data_as(C.POINTER(C.c_uint16))
+        self._call("skinned_mesh_variant_upload", int(variant), C.byref(d))
+        if not hasattr(self, "variant_vertex_counts"):
+            self.variant_vertex_counts = {}
+        self.variant_vertex_counts[int(variant)] = V
+
+    def set_mesh_variants(self, variants, first=0):
+        """One byte per character from `first` on: the mesh its next skin launches use. Asynchronous."""
+        v = np.ascontiguousarray(variants, np.uint8).reshape(-1)
+        self._call("characters_set_mesh_variants", int(first), v.shape[0], ptr(v))
+
+    def lod_select(self, eye, distances):
+        """Variants by distance to `eye`, on the device: the number of thresholds a character's squared distance has reached. Asynchronous."""
+        e = (C.c_double * 3)(*[float(x) for x in eye])
+        dist = np.ascontiguousarray(distances, np.float32).reshape(-1)
+        self._call("lod_select", e, dist.ctypes.data_as(C.POINTER(C.c_float)), dist.shape[0])
+
+    def reserve_vertices(self, n):
+        """Capacity of the three output streams in vertices; 0 = count x the largest uploaded mesh."""
+        self._call("crowd_reserve_vertices", int(n))
+
+    def _device_to_host(self, out, device_ptr):
+        hip = _hip_runtime()
+        if hip.hipMemcpy(out.ctypes.data, device_ptr, out.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+            raise SgeError("hipMemcpy from the device failed")
+        return out
+
+    def vertex_offsets(self):
+        """int64[count + 1] of the newest skin launch: character c owns vertices [off[c], off[c + 1]) of the streams. Synchronises."""
+        p = C.c_void_p()
+        self._call("crowd_vertex_offsets", C.byref(p))
+        self.synchronize()
+        return self._device_to_host(np.empty(self.count + 1, np.int64), p)
+
+    def skin_plan(self):
+        """The plan of the newest skin launch over mesh variants (abi.SkinPlanInfo). Waits for that launch."""
+        info = abi.SkinPlanInfo()
+        self._call("skin_plan_read", C.byref(info))
+        return info
+
+    def skinned_character(self, c, positions=True, normals=True, tangents=True):
+        """Character c's slice of the three streams, by the vertex offsets -> (positions, normals, tangents)."""
+        off = self.vertex_offsets()
+        return self.skinned(int(off[c]), int(off[c + 1] - off[c]), positions, normals, tangents)
 
     def skinning_encode(self, out_positions, out_normals, out_tangents, out_layout, jobs):
         """RTSkinningEncoder.encode: out_* are device pointers (ints) on the product, host arrays' pointers on the oracle;
