@@ -20,7 +20,8 @@
  *
  * Out of scope while a variant >= 1 exists (SGE_ERR_STATE, text via sge_last_error):
  *   - SGE_STAGE_BLAS_REFIT (fused or not), sge_blas_refit, sge_blas_refit_buffers, sge_blas_intersect_batch and
- *     sge_blas_intersect_device: one acceleration structure per variant is not built, and the one of variant 0 does not
+ *     sge_blas_intersect_device, until every uploaded variant has an acceleration structure (sge_amd_variant_blas.h says
+ *     when that is and what opens up then; sge_blas_refit_buffers stays refused): the structure of variant 0 alone does not
  *     describe the ragged streams;
  *   - SGE_STAGE_SKIN on a sub-range of the crowd (first / count other than the whole crowd): the offsets are a scan over all.
  */

@@ -349,6 +349,24 @@ VARIANT_PROTOTYPES = {
     "sge_skin_plan_read": (C.c_int, [VP, P(SkinPlanInfo)]),
 }
 
+
+# include/sge_amd_variant_blas.h: one acceleration structure per mesh variant, the ragged refit and ray queries over mixed variants.
+class BlasVariantLayout(C.Structure):
+    _fields_ = [("ready", i32), ("variants", i32), ("rowStride", i32), ("_pad", i32), ("entryCount", i32 * SGE_MAX_MESH_VARIANTS)]
+
+
+assert C.sizeof(BlasVariantLayout) == 48
+NO_VARIANT = 0xFF  # charVariant record of a character no refit has described
+
+VARIANT_BLAS_PROTOTYPES = {
+    "sge_blas_variant_build": (C.c_int, [VP, i32, VP, i32]),
+    "sge_blas_variant_set_uvs": (C.c_int, [VP, i32, VP, i32]),
+    "sge_blas_variant_info_get": (C.c_int, [VP, i32, P(BlasInfo)]),
+    "sge_blas_variant_layout": (C.c_int, [VP, P(BlasVariantLayout)]),
+    "sge_blas_variant_bounds_download": (C.c_int, [VP, i32, i32, VP, VP]),
+    "sge_blas_variant_buffers": (C.c_int, [VP, P(VP), P(VP), P(VP)]),
+}
+
 LIB_NAME = "libsge_amd.so"
 
 
@@ -382,10 +400,11 @@ def load_library(path=None):
         raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = bind(C.CDLL(path))
-    for name, (res, args) in VARIANT_PROTOTYPES.items():  # (raises AttributeError if one is missing)
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES):
+        for name, (res, args) in table.items():  # (raises AttributeError if one is missing)
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     return lib
 
 

@@ -30,6 +30,20 @@ def upload_character_assets(engine, ybot, rings=22, segments=10, mesh_inv_bind=F
     return built, mesh
 
 
+def synthetic_lod_mesh(engine, built, ybot, rings, segments):
+    """The synthetic skinned mesh of upload_character_assets at another resolution (rings x segments vertices per bone), tangents
+    computed: a COMPLETE mesh with its own index buffer, as a mesh variant with an acceleration structure needs (a vertex subset,
+    assets.decimate_skinned_mesh, keeps few or none of the triangles)."""
+    B = ybot.bone_count
+    local = built["bindLocal"].reshape(B, 4, 4).astype(np.float64)
+    model = np.zeros_like(local)
+    for i in range(B):
+        p = ybot.parent[i]
+        model[i] = local[i] if p < 0 else np.einsum("kr,ck->cr", model[p], local[i])
+    mesh = A.make_synthetic_skinned_mesh(ybot.parent, model.reshape(B, 16).astype(np.float32), rings=rings, segments=segments)
+    return dict(mesh, tangents=engine.compute_tangents(mesh["positions"], mesh["normals"], mesh["uvs"], mesh["indices"]))
+
+
 def upload_ybot_mesh(engine, ybot, path=None):
     """Skeleton, profiles and the real Y-Bot skinned mesh (tests/golden/ybot_skinned.npz = ExternalResources/Y Bot.fbx
     through exporters.export_skinned_mesh) loaded the way SkinnedMeshLoader.buildAsset does; the palette is re-bound

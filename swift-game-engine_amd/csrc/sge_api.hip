@@ -146,6 +146,19 @@ struct sge_context {
     DevBuf dBlasEntryLink, dBlasWideFirst, dBlasWideParent, dBlasWideLevel, dBlasSlotIdx, dBlasSlotTri,
            dBlasIndices, dBlasBounds, dBlasInstances, dBlasRays, dBlasHits, dBlasTileStart, dBlasRoundLen, dBlasRoundCluster, dBlasRoundIds, dBlasWorldBoxes, dBlasUVs, dBlasQueue, dSkinQueue, dBlasInstPoints, dBlasInstMinMax, dBlasInstGrid, dBlasInstOrder, dBlasGroupBoxes;
     bool blasHasUVs = false;
+    // one acceleration structure per mesh variant (include/sge_amd_variant_blas.h). Variant 0's is `blas` above; vblas[1..] are built
+    // by sge_blas_variant_build from the host copy of the variant's source positions. The context is READY (variantBlasReady) when
+    // every uploaded variant has one: then dVarBounds [count][varRowStride][6], dCharVariant [count] and the device table exist.
+    struct VariantBlas {
+        std::vector<float> hostPos;
+        HostBlas host;
+        DevBlas dev{};
+        bool built = false, hasUVs = false;
+        DevBuf entryLink, wideFirst, wideParent, wideLevel, slotIdx, slotTri, indices, tileStart, roundLen, roundCluster, roundIds, uvs;
+    } vblas[SGE_MAX_MESH_VARIANTS];
+    int varRowStride = 0, varBoundsChars = 0;
+    DevVariantBlas hostVarBlasTable[SGE_MAX_MESH_VARIANTS] = {}; // what dVarBlasTable was last uploaded from (outlives the asynchronous copy)
+    DevBuf dVarBlasTable, dVarBounds, dCharVariant, dVarBlasQueue;
     // stats / profiling
     DevBuf dStats, dWaveProf, dOrderHist, dSepAgents, dSepCounts, dSepFlow;
     int separationIterations = 2; float separationMargin = 0.2f, separationHeightMargin = 0.1f; // AgentSeparationSystem.init :2146-2152
@@ -414,13 +427,16 @@ int allocCrowdOutputs(sge_context* c) {
     return SGE_OK;
 }
 
+bool variantBlasReady(const sge_context* c);
 // Per-character buffers of the acceleration structure: boxes (zeroed until the first refit) and instance matrices (identity).
 int ensureBlasBuffers(sge_context* c) {
     if (c->blas.entryCount == 0 || c->crowd.count == 0) return SGE_OK;
     const size_t N = (size_t)c->crowd.count, rowBytes = (size_t)(c->blas.entryCount + 1) * 24;
     int rc;
-    if ((rc = c->dBlasBounds.alloc(N * rowBytes)) != SGE_OK) return rc;
-    SGE_HIP(hipMemsetAsync(c->dBlasBounds.p, 0, N * rowBytes, c->stream));
+    if (!variantBlasReady(c)) { // (ready: the boxes are dVarBounds, nothing reads variant 0's uniform table)
+        if ((rc = c->dBlasBounds.alloc(N * rowBytes)) != SGE_OK) return rc;
+        SGE_HIP(hipMemsetAsync(c->dBlasBounds.p, 0, N * rowBytes, c->stream));
+    }
     if (c->blasBoundsChars != c->crowd.count) {
         std::vector<float> ident(N * 16, 0.0f);
         for (size_t i = 0; i < N; ++i) ident[i * 16] = ident[i * 16 + 5] = ident[i * 16 + 10] = ident[i * 16 + 15] = 1.0f;
@@ -429,6 +445,64 @@ int ensureBlasBuffers(sge_context* c) {
         c->blasBoundsChars = c->crowd.count;
     }
     return SGE_OK;
+}
+
+// include/sge_amd_variant_blas.h, "Ready": mesh variants exist and every one of them has a structure newer than its mesh
+bool variantBlasReady(const sge_context* c) {
+    if (c->extraVariants == 0 || c->blas.entryCount == 0) return false;
+    for (int v = 1; v <= c->extraVariants; ++v) if (!c->vblas[v].built) return false;
+    return true;
+}
+const DevBlas& variantDevBlas(const sge_context* c, int v) { return v == 0 ? c->blas : c->vblas[v].dev; }
+// The device table of the ragged kernels (topology, index buffer, uvs per variant) and the per-character buffers: boxes (zeroed)
+// and the charVariant record (0xFF: no refit has described the character). Nothing to do while not ready. Callers have synchronised.
+int ensureVariantBlasBuffers(sge_context* c, bool resetBoxes) {
+    if (!variantBlasReady(c)) return SGE_OK;
+    DevVariantBlas* rows = c->hostVarBlasTable;
+    for (int v = 0; v < SGE_MAX_MESH_VARIANTS; ++v) rows[v] = DevVariantBlas{};
+    int stride = 0;
+    for (int v = 0; v <= c->extraVariants; ++v) {
+        rows[v].blas = variantDevBlas(c, v);
+        rows[v].indices = v == 0 ? c->dBlasIndices.as<uint32_t>() : c->vblas[v].indices.as<uint32_t>();
+        rows[v].uvs = v == 0 ? (c->blasHasUVs ? c->dBlasUVs.as<float>() : nullptr) : (c->vblas[v].hasUVs ? c->vblas[v].uvs.as<float>() : nullptr);
+        stride = std::max(stride, rows[v].blas.entryCount + 1);
+    }
+    int rc;
+    if ((rc = upload(c->dVarBlasTable, rows, sizeof(c->hostVarBlasTable), c->stream)) != SGE_OK) return rc;
+    c->dBlasBounds.release(); // variant 0's uniform box table: nothing reads it from here on (sge_blas_build allocates it again)
+    if ((rc = c->dVarBlasQueue.alloc((size_t)SGE_MAX_MESH_VARIANTS * 64 * 2)) != SGE_OK) return rc; // [0]: sge_tick's launches, [1]: the stand-alone refit's
+    const size_t N = (size_t)c->crowd.count;
+    if (resetBoxes || stride != c->varRowStride || c->varBoundsChars != c->crowd.count) {
+        c->varRowStride = stride;
+        c->varBoundsChars = c->crowd.count;
+        if (N > 0) {
+            if ((rc = c->dVarBounds.alloc(N * (size_t)stride * 24)) != SGE_OK) return rc;
+            if ((rc = c->dCharVariant.alloc(N)) != SGE_OK) return rc;
+            SGE_HIP(hipMemsetAsync(c->dVarBounds.p, 0, N * (size_t)stride * 24, c->stream));
+            SGE_HIP(hipMemsetAsync(c->dCharVariant.p, 0xFF, N, c->stream));
+        }
+    }
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    return SGE_OK;
+}
+// the refit over the ragged streams of the newest skin launch, on `s`
+int launchVariantRefit(sge_context* c, int layout, int queueSet, hipStream_t s) {
+    DevBlas blas[SGE_MAX_MESH_VARIANTS];
+    for (int v = 0; v <= c->extraVariants; ++v) blas[v] = variantDevBlas(c, v);
+    RaggedRefitLaunch L{blas, 1 + c->extraVariants, c->dSkinPlan.as<SkinPlan>(), c->dVariantLists.as<int>(), c->dVertexOff.as<long long>(),
+                        c->dOutPos.p, layout, (long long)outputCapacity(c), c->crowd.count, c->dVarBounds.as<float>(), c->varRowStride,
+                        c->dCharVariant.as<uint8_t>(), c->dVarBlasQueue.as<int>() + queueSet * SGE_MAX_MESH_VARIANTS * 16};
+    return launch_blas_refit_ragged(L, s);
+}
+RaggedTrace variantTrace(sge_context* c) {
+    RaggedTrace R{};
+    R.table = c->dVarBlasTable.as<DevVariantBlas>();
+    R.charVariant = c->dCharVariant.as<uint8_t>();
+    R.off = c->dVertexOff.as<long long>();
+    R.rowStride = c->varRowStride;
+    R.T = BlasTrace{DevBlas{}, c->dOutPos.p, c->dOutNrm.p, c->dOutTan.as<float>(), nullptr, c->outLayoutAllocated,
+                    c->dVarBounds.as<float>(), c->dBlasInstances.as<float>(), c->crowd.count, nullptr, nullptr};
+    return R;
 }
 
 // ---- agent grid (uniform XZ cells over the gathered snapshot) ---------------
@@ -563,14 +637,20 @@ int buildAgentGrid(sge_context* c) {
 // agent sweeps use (over the boxes' centres), one box per 64 consecutive characters of THAT order, one per 64 such groups. A ray
 // then tests 64 super-groups, 64 groups, 64 instances per step where the flat form scanned ceil(N / 64) index groups: 250,000
 // characters are 62 super-groups. Fills the trace's pointers; everything on the context's stream.
-int buildInstanceLevel(sge_context* c, BlasTrace& T) {
+int buildInstanceLevel(sge_context* c, BlasTrace& T, const RaggedTrace* ragged = nullptr) {
     const int N = c->crowd.count, groups = (N + 63) / 64, supers = (groups + 63) / 64;
     int rc;
     if ((rc = c->dBlasWorldBoxes.alloc(((size_t)N + groups) * 24)) != SGE_OK) return rc;
     if ((rc = c->dBlasInstPoints.alloc((size_t)N * sizeof(sge_agent_state))) != SGE_OK) return rc;
     if ((rc = c->dBlasGroupBoxes.alloc(((size_t)groups + supers) * 24)) != SGE_OK) return rc;
     T.worldBoxes = c->dBlasWorldBoxes.as<float>();
-    launch_blas_world_boxes(T, c->dBlasWorldBoxes.as<float>(), c->stream);
+    if (ragged) { // mesh variants: the root row and the record of every character are its own (T is ragged->T)
+        RaggedTrace R = *ragged;
+        R.T = T;
+        launch_blas_world_boxes_ragged(R, c->dBlasWorldBoxes.as<float>(), c->stream);
+    } else {
+        launch_blas_world_boxes(T, c->dBlasWorldBoxes.as<float>(), c->stream);
+    }
     const bool flat = getenv("SGE_BLAS_FLAT_INSTANCES") != nullptr; // experiments / tests: the flat scan of 64 consecutive indices (read per call)
     if (flat) { T.instOrder = nullptr; return SGE_OK; }
     launch_blas_instance_points(c->dBlasWorldBoxes.as<float>(), N, c->dBlasInstPoints.as<sge_agent_state>(), c->stream);
@@ -689,6 +769,9 @@ void sge_context_destroy(sge_context* c) {
     for (DevBuf* b : bufs) b->release();
     for (int v = 0; v < SGE_MAX_MESH_VARIANTS; ++v)
         for (DevBuf* b : {&c->dVarPos[v], &c->dVarNrm[v], &c->dVarTan[v], &c->dVarIdx[v], &c->dVarWgt[v]}) b->release();
+    for (auto& vb : c->vblas)
+        for (DevBuf* b : {&vb.entryLink, &vb.wideFirst, &vb.wideParent, &vb.wideLevel, &vb.slotIdx, &vb.slotTri, &vb.indices, &vb.tileStart, &vb.roundLen, &vb.roundCluster, &vb.roundIds, &vb.uvs}) b->release();
+    for (DevBuf* b : {&c->dVarBlasTable, &c->dVarBounds, &c->dCharVariant, &c->dVarBlasQueue}) b->release();
     for (DevBuf* b : {&c->dVariantTable, &c->dVariantOf, &c->dVariantSnap[0], &c->dVariantSnap[1], &c->dVertexOff, &c->dVariantLists, &c->dSkinPlan}) b->release();
     for (hipEvent_t e : {c->evVariantSnap, c->evPlanDone[0], c->evPlanDone[1], c->variantStage[0].copied, c->variantStage[1].copied}) if (e) (void)hipEventDestroy(e);
     for (auto& st : c->variantStage) if (st.host) (void)hipHostFree(st.host);
@@ -968,6 +1051,9 @@ int sge_skinned_mesh_variant_upload(sge_context* c, int32_t variant, const sge_s
                                       c->dVarIdx[variant].as<uint16_t>(), c->dVarWgt[variant].as<float>()};
     c->extraVariants = std::max(c->extraVariants, (int)variant);
     c->planValid = false;
+    c->vblas[variant].hostPos.assign(d->positions, d->positions + V * 3); // sge_blas_variant_build builds the topology from them
+    c->vblas[variant].built = false; // the structure of the mesh this one replaces does not describe it: not ready again
+    c->vblas[variant].hasUVs = false;
     if ((rc = refreshVariantTable(c)) != SGE_OK) return rc;
     if (c->crowd.count > 0) return allocCrowdOutputs(c);
     return SGE_OK;
@@ -1485,6 +1571,7 @@ int sge_characters_resize(sge_context* c, int32_t count) {
     if ((rc = refreshVariantTable(c)) != SGE_OK) return rc;
     if (c->mesh.vertexCount > 0 && (rc = allocCrowdOutputs(c)) != SGE_OK) return rc;
     if ((rc = ensureBlasBuffers(c)) != SGE_OK) return rc;
+    if ((rc = ensureVariantBlasBuffers(c, true)) != SGE_OK) return rc;
     SGE_HIP(hipStreamSynchronize(c->stream));
     return SGE_OK;
 }
@@ -1762,7 +1849,7 @@ int sge_tick(sge_context* c, const sge_tick_desc* d) {
     (void)hipSetDevice(c->device);
     const uint32_t st = d->stages;
     if (c->extraVariants > 0) { // include/sge_amd_variants.h, "Out of scope"
-        if (st & SGE_STAGE_BLAS_REFIT) { set_error("SGE_STAGE_BLAS_REFIT is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
+        if ((st & SGE_STAGE_BLAS_REFIT) && !variantBlasReady(c)) { set_error("SGE_STAGE_BLAS_REFIT is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
         if ((st & SGE_STAGE_SKIN) && (first != 0 || count != c->crowd.count)) { set_error("SGE_STAGE_SKIN works on the whole crowd while mesh variants are uploaded (first = 0, count = all): the vertex offsets are a scan over every character"); return SGE_ERR_STATE; }
     }
     // Overlap mode, a whole-crowd tick with move + pose + skin: the pose launch goes to the pose stream and reads the move stage's
@@ -1933,7 +2020,7 @@ int sge_tick(sge_context* c, const sge_tick_desc* d) {
         const bool refit = (st & SGE_STAGE_BLAS_REFIT) != 0;
         if (refit && c->blas.entryCount == 0) { set_error("SGE_STAGE_BLAS_REFIT needs sge_blas_build"); return SGE_ERR_STATE; }
         float* boxes = refit ? c->dBlasBounds.as<float>() + (size_t)first * (c->blas.entryCount + 1) * 6 : nullptr;
-        if (refit && (c->fuseBlas == 2 || (c->fuseBlas == 1 && !overlap))) {
+        if (refit && !variants && (c->fuseBlas == 2 || (c->fuseBlas == 1 && !overlap))) {
             // one launch: the LBS kernel keeps every position it computes in an LDS tile and reduces the boxes from there
             Bracket br(c, &c->evSkin, ss);
             int rc = launch_skin_refit(L, c->blas, boxes, c->dBlasQueue.as<int>(), ss, overlap ? c->overlapFusedWorkgroups : 0);
@@ -1958,6 +2045,12 @@ int sge_tick(sge_context* c, const sge_tick_desc* d) {
                     if (form <= 0) { set_error("the skin launch over mesh variants could not be set up"); return SGE_ERR_STATE; }
                     if (overlap) c->planPending[planSlot] = true;
                     c->planValid = true;
+                    // The records name the variant whose structure a character's boxes describe, and the ray kernels pair them with
+                    // the offsets this launch has just rewritten. Without a refit behind it the pairs no longer match (another
+                    // assignment or another cut moves off[c] under a record of the old plan): no character has a structure until
+                    // the next refit. (With the refit stage launch_blas_refit_ragged does the same in front of its kernels.)
+                    if (!refit && variantBlasReady(c) && c->dCharVariant.p)
+                        SGE_HIP(hipMemsetAsync(c->dCharVariant.p, 0xFF, (size_t)c->crowd.count, ss));
                 } else {
                     form = launch_skin(L, ss, overlap ? c->overlapSkinWorkgroups : 0, c->dSkinQueue.as<int>(), quarters, c->residentSkinCharsPerUnit);
                 }
@@ -1967,7 +2060,9 @@ int sge_tick(sge_context* c, const sge_tick_desc* d) {
             }
             if (refit) { // RTAccelerationBuilder.build is enqueued right behind the skinning encoder (RayTracingScene.swift:35-43)
                 Bracket br(c, &c->evBlas, ss);
-                int rc = launch_blas_refit(c->blas, c->dOutPos.p, c->skinLayout, (long long)first * c->mesh.vertexCount, count, boxes, c->dBlasQueue.as<int>(), ss);
+                // (mesh variants: one ragged launch per variant over the plan the skin launch has just left, never fused)
+                int rc = variants ? launchVariantRefit(c, c->skinLayout, 0, ss)
+                                  : launch_blas_refit(c->blas, c->dOutPos.p, c->skinLayout, (long long)first * c->mesh.vertexCount, count, boxes, c->dBlasQueue.as<int>(), ss);
                 if (rc != SGE_OK) return rc;
             }
         }
@@ -2015,6 +2110,7 @@ int sge_blas_build(sge_context* c, const uint32_t* indices, int32_t index_count)
                       h.tileVerts, h.tileCount, h.tileCap, c->dBlasTileStart.as<int>(), c->dBlasRoundLen.as<int>(), c->dBlasRoundCluster.as<int>(), c->dBlasRoundIds.as<uint32_t>()};
     c->blasBoundsChars = 0;
     c->blasHasUVs = false;
+    for (auto& vb : c->vblas) vb.built = false; // include/sge_amd_variant_blas.h, "Ready": sge_blas_build starts over
     return ensureBlasBuffers(c);
 }
 
@@ -2027,7 +2123,7 @@ int sge_blas_set_uvs(sge_context* c, const float* uvs, int32_t vertex_count) {
     if (rc != SGE_OK) return rc;
     SGE_HIP(hipStreamSynchronize(c->stream));
     c->blasHasUVs = true;
-    return SGE_OK;
+    return ensureVariantBlasBuffers(c, false); // (ready: variant 0's row of the device table)
 }
 
 int sge_blas_info_get(sge_context* c, sge_blas_info* info) {
@@ -2040,7 +2136,19 @@ int sge_blas_info_get(sge_context* c, sge_blas_info* info) {
 
 int sge_blas_refit(sge_context* c, int32_t first, int32_t count) {
     SGE_RANGE_CHECK();
-    if (c->extraVariants > 0) { set_error("sge_blas_refit is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
+    if (c->extraVariants > 0) {
+        if (!variantBlasReady(c)) { set_error("sge_blas_refit is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
+        if (first != 0 || count != c->crowd.count) { set_error("sge_blas_refit works on the whole crowd while mesh variants are uploaded (first = 0, count = all): the lists of the plan cover every character"); return SGE_ERR_STATE; }
+        if (!c->planValid) { set_error("sge_blas_refit: no skin stage with mesh variants has run"); return SGE_ERR_STATE; }
+        if (count == 0) return SGE_OK;
+        (void)hipSetDevice(c->device);
+        { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
+        Bracket br(c, &c->evBlas);
+        int rc = launchVariantRefit(c, c->outLayoutAllocated, 1, c->stream);
+        if (rc != SGE_OK) return rc;
+        SGE_HIP(hipGetLastError());
+        return SGE_OK;
+    }
     if (c->blas.entryCount == 0) { set_error("sge_blas_refit needs sge_blas_build"); return SGE_ERR_STATE; }
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
@@ -2058,7 +2166,7 @@ int sge_blas_refit_buffers(sge_context* c, const void* d_positions, int32_t layo
         set_error("sge_blas_refit_buffers: bad argument");
         return SGE_ERR_INVALID;
     }
-    if (c->extraVariants > 0) { set_error("sge_blas_refit_buffers is not available while mesh variants are uploaded: one acceleration structure per variant is not built"); return SGE_ERR_STATE; }
+    if (c->extraVariants > 0) { set_error("sge_blas_refit_buffers is not available while mesh variants are uploaded: caller-owned buffers carry no vertex offsets"); return SGE_ERR_STATE; }
     if (c->blas.entryCount == 0) { set_error("sge_blas_refit_buffers needs sge_blas_build"); return SGE_ERR_STATE; }
     (void)hipSetDevice(c->device);
     { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
@@ -2073,6 +2181,7 @@ int sge_blas_bounds_download(sge_context* c, int32_t first, int32_t count, float
     SGE_RANGE_CHECK();
     if (!bounds) { set_error("sge_blas_bounds_download: bad argument"); return SGE_ERR_INVALID; }
     if (c->blas.entryCount == 0) { set_error("no acceleration structure built"); return SGE_ERR_STATE; }
+    if (variantBlasReady(c)) { set_error("sge_blas_bounds_download: its rows are variant 0's; with mesh variants use sge_blas_variant_bounds_download"); return SGE_ERR_STATE; }
     (void)hipSetDevice(c->device);
     { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
     const size_t row = (size_t)(c->blas.entryCount + 1) * 24;
@@ -2099,7 +2208,8 @@ int sge_blas_instances_upload(sge_context* c, int32_t first, int32_t count, cons
 
 int sge_blas_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t count, sge_blas_hit* hits) {
     if (!c || count < 0 || (count > 0 && (!rays || !hits))) { set_error("sge_blas_intersect_batch: bad argument"); return SGE_ERR_INVALID; }
-    if (c->extraVariants > 0) { set_error("sge_blas_intersect_batch is not available while mesh variants are uploaded: the boxes and the index buffer are variant 0's, the streams are ragged"); return SGE_ERR_STATE; }
+    const bool ragged = variantBlasReady(c);
+    if (c->extraVariants > 0 && !ragged) { set_error("sge_blas_intersect_batch is not available while mesh variants are uploaded: the boxes and the index buffer are variant 0's, the streams are ragged"); return SGE_ERR_STATE; }
     if (c->blas.entryCount == 0 || c->crowd.count == 0) { set_error("sge_blas_intersect_batch needs sge_blas_build and characters"); return SGE_ERR_STATE; }
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
@@ -2112,8 +2222,14 @@ int sge_blas_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t c
     BlasTrace T{c->blas, c->dOutPos.p, c->dOutNrm.p, c->dOutTan.as<float>(), c->dBlasIndices.as<uint32_t>(), c->outLayoutAllocated,
                 c->dBlasBounds.as<float>(), c->dBlasInstances.as<float>(), c->crowd.count, nullptr,
                 c->blasHasUVs ? c->dBlasUVs.as<float>() : nullptr};
-    if (anyInstance && (rc = buildInstanceLevel(c, T)) != SGE_OK) return rc;
-    launch_blas_intersect(T, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>(), anyInstance, c->stream);
+    if (ragged) {
+        RaggedTrace R = variantTrace(c);
+        if (anyInstance && (rc = buildInstanceLevel(c, R.T, &R)) != SGE_OK) return rc;
+        launch_blas_intersect_ragged(R, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>(), anyInstance, c->stream);
+    } else {
+        if (anyInstance && (rc = buildInstanceLevel(c, T)) != SGE_OK) return rc;
+        launch_blas_intersect(T, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>(), anyInstance, c->stream);
+    }
     SGE_HIP(hipGetLastError());
     SGE_HIP(hipMemcpyAsync(hits, c->dBlasHits.p, (size_t)count * sizeof(sge_blas_hit), hipMemcpyDeviceToHost, c->stream));
     SGE_HIP(hipStreamSynchronize(c->stream));
@@ -2122,7 +2238,8 @@ int sge_blas_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t c
 
 int sge_blas_intersect_device(sge_context* c, const void* d_rays, int32_t count, void* d_hits, int32_t any_instance) {
     if (!c || count < 0 || (count > 0 && (!d_rays || !d_hits))) { set_error("sge_blas_intersect_device: bad argument"); return SGE_ERR_INVALID; }
-    if (c->extraVariants > 0) { set_error("sge_blas_intersect_device is not available while mesh variants are uploaded: the boxes and the index buffer are variant 0's, the streams are ragged"); return SGE_ERR_STATE; }
+    const bool ragged = variantBlasReady(c);
+    if (c->extraVariants > 0 && !ragged) { set_error("sge_blas_intersect_device is not available while mesh variants are uploaded: the boxes and the index buffer are variant 0's, the streams are ragged"); return SGE_ERR_STATE; }
     if (c->blas.entryCount == 0 || c->crowd.count == 0) { set_error("sge_blas_intersect_device needs sge_blas_build and characters"); return SGE_ERR_STATE; }
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
@@ -2131,9 +2248,114 @@ int sge_blas_intersect_device(sge_context* c, const void* d_rays, int32_t count,
     BlasTrace T{c->blas, c->dOutPos.p, c->dOutNrm.p, c->dOutTan.as<float>(), c->dBlasIndices.as<uint32_t>(), c->outLayoutAllocated,
                 c->dBlasBounds.as<float>(), c->dBlasInstances.as<float>(), c->crowd.count, nullptr,
                 c->blasHasUVs ? c->dBlasUVs.as<float>() : nullptr};
-    if (any_instance && (rc = buildInstanceLevel(c, T)) != SGE_OK) return rc;
-    launch_blas_intersect(T, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits), any_instance != 0, c->stream);
+    if (ragged) {
+        RaggedTrace R = variantTrace(c);
+        if (any_instance && (rc = buildInstanceLevel(c, R.T, &R)) != SGE_OK) return rc;
+        launch_blas_intersect_ragged(R, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits), any_instance != 0, c->stream);
+    } else {
+        if (any_instance && (rc = buildInstanceLevel(c, T)) != SGE_OK) return rc;
+        launch_blas_intersect(T, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits), any_instance != 0, c->stream);
+    }
     SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+
+// ---- one acceleration structure per mesh variant (include/sge_amd_variant_blas.h) ------------
+int sge_blas_variant_build(sge_context* c, int32_t variant, const uint32_t* indices, int32_t index_count) {
+    if (!c || !indices || index_count <= 0) { set_error("sge_blas_variant_build: bad argument"); return SGE_ERR_INVALID; }
+    if (variant == 0) { set_error("sge_blas_variant_build: variant 0 is built through sge_blas_build"); return SGE_ERR_INVALID; }
+    if (variant < 0 || variant > c->extraVariants) { set_error("sge_blas_variant_build: mesh variant was never uploaded"); return SGE_ERR_INVALID; }
+    if (c->blas.entryCount == 0) { set_error("sge_blas_variant_build needs sge_blas_build (variant 0) first"); return SGE_ERR_STATE; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    sge_context::VariantBlas& vb = c->vblas[variant];
+    const int V = c->variantMesh[variant].vertexCount;
+    std::string err;
+    HostBlas hb;
+    if (!hb.build(vb.hostPos.data(), V, indices, index_count, err)) { set_error(err); return SGE_ERR_INVALID; }
+    if (hb.levels * 63 + 1 > kBlasTraversalStackCap) { set_error("sge_blas_variant_build: hierarchy too deep for the closest-hit traversal stack"); return SGE_ERR_CAPACITY; }
+    int rc;
+    hipStream_t s = c->stream;
+    vb.built = false;
+    if ((rc = upload(vb.entryLink, hb.entryLink.data(), hb.entryLink.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.wideFirst, hb.wideFirst.data(), hb.wideFirst.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.wideParent, hb.wideParentEntry.data(), hb.wideParentEntry.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.wideLevel, hb.wideLevelStart.data(), hb.wideLevelStart.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.slotIdx, hb.slotIndices.data(), hb.slotIndices.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.slotTri, hb.slotTriangle.data(), hb.slotTriangle.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.indices, indices, (size_t)index_count * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.tileStart, hb.tileRoundStart.data(), hb.tileRoundStart.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.roundLen, hb.roundLen.data(), hb.roundLen.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.roundCluster, hb.roundCluster.data(), hb.roundCluster.size() * 4, s)) != SGE_OK) return rc;
+    if ((rc = upload(vb.roundIds, hb.roundIds.data(), hb.roundIds.size() * 4, s)) != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(s));
+    vb.host = std::move(hb);
+    const HostBlas& h = vb.host;
+    vb.dev = DevBlas{h.entryCount(), h.wideCount(), h.triCount, h.vertexCount, h.clusterCount, h.levels,
+                     vb.entryLink.as<int2>(), vb.wideFirst.as<int>(), vb.wideParent.as<int>(), vb.wideLevel.as<int>(),
+                     vb.slotIdx.as<uint32_t>(), vb.slotTri.as<uint32_t>(),
+                     h.tileVerts, h.tileCount, h.tileCap, vb.tileStart.as<int>(), vb.roundLen.as<int>(), vb.roundCluster.as<int>(), vb.roundIds.as<uint32_t>()};
+    vb.built = true;
+    vb.hasUVs = false;
+    return ensureVariantBlasBuffers(c, true); // (ready now: boxes zeroed, every record 0xFF until the first refit)
+}
+
+int sge_blas_variant_set_uvs(sge_context* c, int32_t variant, const float* uvs, int32_t vertex_count) {
+    if (!c || !uvs) { set_error("sge_blas_variant_set_uvs: bad argument"); return SGE_ERR_INVALID; }
+    if (variant == 0) return sge_blas_set_uvs(c, uvs, vertex_count);
+    if (variant < 0 || variant > c->extraVariants) { set_error("sge_blas_variant_set_uvs: mesh variant was never uploaded"); return SGE_ERR_INVALID; }
+    sge_context::VariantBlas& vb = c->vblas[variant];
+    if (!vb.built) { set_error("sge_blas_variant_set_uvs needs sge_blas_variant_build"); return SGE_ERR_STATE; }
+    if (vertex_count != c->variantMesh[variant].vertexCount) { set_error("sge_blas_variant_set_uvs: vertex count differs from the variant's mesh"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    int rc = upload(vb.uvs, uvs, (size_t)vertex_count * 8, c->stream);
+    if (rc != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    vb.hasUVs = true;
+    return ensureVariantBlasBuffers(c, false);
+}
+
+int sge_blas_variant_info_get(sge_context* c, int32_t variant, sge_blas_info* info) {
+    if (!c || !info) { set_error("sge_blas_variant_info_get: bad argument"); return SGE_ERR_INVALID; }
+    if (variant == 0) return sge_blas_info_get(c, info);
+    if (variant < 0 || variant > c->extraVariants) { set_error("sge_blas_variant_info_get: mesh variant was never uploaded"); return SGE_ERR_INVALID; }
+    if (!c->vblas[variant].built) { set_error("no acceleration structure built for this variant"); return SGE_ERR_STATE; }
+    const HostBlas& h = c->vblas[variant].host;
+    *info = sge_blas_info{h.triCount, h.clusterCount, h.entryCount(), h.wideCount(), h.levels, (int32_t)h.vertexEntries.size()};
+    return SGE_OK;
+}
+
+int sge_blas_variant_layout(sge_context* c, struct sge_blas_variant_layout* out) {
+    if (!c || !out) { set_error("sge_blas_variant_layout: bad argument"); return SGE_ERR_INVALID; }
+    memset(out, 0, sizeof(*out));
+    out->ready = variantBlasReady(c) ? 1 : 0;
+    out->variants = variantsUploaded(c);
+    out->rowStride = out->ready ? c->varRowStride : 0;
+    out->entryCount[0] = c->blas.entryCount;
+    for (int v = 1; v <= c->extraVariants; ++v) out->entryCount[v] = c->vblas[v].built ? c->vblas[v].dev.entryCount : 0;
+    return SGE_OK;
+}
+
+int sge_blas_variant_bounds_download(sge_context* c, int32_t first, int32_t count, float* bounds, uint8_t* variants) {
+    SGE_RANGE_CHECK();
+    if (!variantBlasReady(c)) { set_error("sge_blas_variant_bounds_download: not every mesh variant has an acceleration structure (sge_blas_build, sge_blas_variant_build)"); return SGE_ERR_STATE; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    if (count == 0) return SGE_OK;
+    const size_t row = (size_t)c->varRowStride * 24;
+    if (bounds) SGE_HIP(hipMemcpy(bounds, reinterpret_cast<const char*>(c->dVarBounds.p) + (size_t)first * row, (size_t)count * row, hipMemcpyDeviceToHost));
+    if (variants) SGE_HIP(hipMemcpy(variants, c->dCharVariant.as<uint8_t>() + first, (size_t)count, hipMemcpyDeviceToHost));
+    return SGE_OK;
+}
+
+int sge_blas_variant_buffers(sge_context* c, void** d_bounds, void** d_char_variants, void* d_indices[SGE_MAX_MESH_VARIANTS]) {
+    if (!c) { set_error("sge_blas_variant_buffers: bad argument"); return SGE_ERR_INVALID; }
+    if (!variantBlasReady(c)) { set_error("sge_blas_variant_buffers: not every mesh variant has an acceleration structure (sge_blas_build, sge_blas_variant_build)"); return SGE_ERR_STATE; }
+    if (d_bounds) *d_bounds = c->dVarBounds.p;
+    if (d_char_variants) *d_char_variants = c->dCharVariant.p;
+    if (d_indices)
+        for (int v = 0; v < SGE_MAX_MESH_VARIANTS; ++v) d_indices[v] = v == 0 ? c->dBlasIndices.p : (v <= c->extraVariants ? c->vblas[v].indices.p : nullptr);
     return SGE_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/sge_amd.h"
 #include "../../include/sge_amd_variants.h"
+#include "../../include/sge_amd_variant_blas.h"
 #include "sge_math.hpp"
 
 namespace sge {
@@ -23,6 +24,7 @@ static_assert(sizeof(sge_capsule_overlap_hit) == 56, "layout");
 static_assert(sizeof(sge_bvh_node) == 44, "layout");
 static_assert(sizeof(sge_tick_desc) == 32, "layout");
 static_assert(sizeof(sge_skin_plan_info) == 64, "layout");
+static_assert(sizeof(struct sge_blas_variant_layout) == 48, "layout");
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
@@ -422,5 +424,36 @@ void launch_blas_world_boxes(const BlasTrace& T, float* worldBoxes, hipStream_t 
 void launch_blas_instance_points(const float* worldBoxes, int chars, sge_agent_state* out, hipStream_t s);
 // boxes of the groups of 64 consecutive entries of `order`, and of 64 consecutive groups
 void launch_blas_group_boxes(const float* worldBoxes, const int* order, int chars, float* groupBoxes, float* superBoxes, hipStream_t s);
+
+// ---- acceleration structures of a crowd with mesh variants (include/sge_amd_variant_blas.h, sge_blas_variants.hip) ---- //
+// One row per uploaded variant, in device memory: the ragged closest-hit and world-box kernels index it with the character's record.
+struct DevVariantBlas {
+    DevBlas blas;
+    const uint32_t* indices; // [T][3] in primitive order
+    const float* uvs;        // [V][2] or null
+};
+struct RaggedRefitLaunch {
+    const DevBlas* blas; int variants;  // host array, one per uploaded variant
+    const SkinPlan* plan;               // device: written by the plan kernel of the newest skin launch
+    const int* lists;                   // [chars] characters grouped by variant (kept characters only)
+    const long long* off;               // [chars + 1]
+    const void* positions; int layout;  // the ragged stream
+    long long capacityVertices;         // of the stream: no vertex at or beyond it is read
+    int chars;
+    float* bounds; int rowStride;       // [chars][rowStride][6]
+    uint8_t* charVariant;               // [chars]
+    int* queues;                        // SGE_MAX_MESH_VARIANTS device ints, 64 bytes apart (ticket counters, zeroed by the launcher)
+};
+// charVariant = 0xFF, then one blas_refit_ragged_kernel per uploaded variant, all on `s`
+int launch_blas_refit_ragged(const RaggedRefitLaunch& L, hipStream_t s);
+struct RaggedTrace {
+    const DevVariantBlas* table;        // device
+    const uint8_t* charVariant;         // [chars] device: 0xFF = no boxes (never entered)
+    const long long* off;               // [chars + 1] device
+    int rowStride;
+    BlasTrace T;                        // blas / indices / uvs unused; bounds = [chars][rowStride][6]
+};
+void launch_blas_world_boxes_ragged(const RaggedTrace& R, float* worldBoxes, hipStream_t s);
+void launch_blas_intersect_ragged(RaggedTrace R, const sge_blas_ray* d_rays, int n, sge_blas_hit* d_hits, bool anyInstance, hipStream_t s);
 
 } // namespace sge

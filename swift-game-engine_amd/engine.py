@@ -512,6 +512,38 @@ class CharacterEngine:
         """Rays / hits already in device memory (blas_ray_dtype / blas_hit_dtype records); asynchronous on the context's stream."""
         self._call("blas_intersect_device", C.c_void_p(d_rays), int(count), C.c_void_p(d_hits), int(bool(any_instance)))
 
+    # -- one structure per mesh variant (include/sge_amd_variant_blas.h; product only) -- #
+    def blas_variant_build(self, variant, indices):
+        """encoder.build for mesh variant 1..7 (variant 0: blas_build) from its uploaded positions and `indices` -> abi.BlasInfo."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._call("blas_variant_build", int(variant), ptr(idx), idx.shape[0])
+        return self.blas_variant_info(variant)
+
+    def blas_variant_set_uvs(self, variant, uvs):
+        u = np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+        self._call("blas_variant_set_uvs", int(variant), ptr(u), u.shape[0])
+
+    def blas_variant_info(self, variant):
+        info = abi.BlasInfo()
+        self._call("blas_variant_info_get", int(variant), C.byref(info))
+        return info
+
+    def blas_variant_layout(self):
+        """abi.BlasVariantLayout: ready, variants, rowStride and every variant's entryCount."""
+        lay = abi.BlasVariantLayout()
+        self._call("blas_variant_layout", C.byref(lay))
+        return lay
+
+    def blas_variant_bounds(self, first=0, count=None):
+        """(bounds [count][rowStride][6], charVariant [count]) of the newest refit over mesh variants: character c's rows
+        0 .. entryCount_v are meaningful, v = charVariant[c] (abi.NO_VARIANT: none). Synchronises."""
+        count = self.count - first if count is None else count
+        lay = self.blas_variant_layout()
+        bounds = np.zeros((count, lay.rowStride, 6), np.float32)
+        variants = np.zeros(count, np.uint8)
+        self._call("blas_variant_bounds_download", first, count, ptr(bounds), ptr(variants))
+        return bounds, variants
+
     def blas_profile(self, reset=True):
         ms, n = C.c_double(0), C.c_int64(0)
         self._call("blas_profile_read", C.byref(ms), C.byref(n), int(reset))
