@@ -205,3 +205,37 @@ class _SyntheticRig:
 
     def profile_index(self, name):
         return self.profile_names.index(name)
+
+
+class ExplicitRig:
+    """_SyntheticRig's sibling with nothing random in its shape: the hierarchy, the pre-rotations, the semantic bones and every
+    profile (order, cycle, present bones, coefficient counts and coefficients) are given — what the pose kernel's launch forms are
+    reached with on purpose (tests/pose_cases.py). Same attributes as assets.YBotAssets."""
+
+    def __init__(self, parent, translations, pre_rotation_degrees, profiles, pelvis_index=0, lean_index=-1,
+                 root_fix_degrees=(0, 180, 0), unit_scale=0.026, zero_root=True):
+        self.parent = np.ascontiguousarray(parent, np.int32)
+        bones = len(self.parent)
+        assert self.parent[0] == -1 and all(-1 <= self.parent[i] < i for i in range(bones))
+        self.names = ["bone%03d" % i for i in range(bones)]
+        self.translations = np.ascontiguousarray(translations, np.float32).reshape(bones, 3)
+        self.pre_rotation_degrees = np.ascontiguousarray(pre_rotation_degrees, np.float32).reshape(bones, 3)
+        self.unit_scale = unit_scale
+        self.root_fix_degrees = np.array(root_fix_degrees, np.float32)
+        self.zero_root = zero_root
+        self.pelvis_index, self.lean_index = pelvis_index, lean_index
+        self.profiles = []
+        for k, p in enumerate(profiles):
+            q = {"name": p.get("name", "profile%02d" % k), "order": int(p["order"]), "cycleDuration": float(p["cycleDuration"]), "sampleFps": 30,
+                 "bonePresent": np.ascontiguousarray(p["bonePresent"], np.uint8), "coeffCount": np.ascontiguousarray(p["coeffCount"], np.uint8),
+                 "coeffs": np.ascontiguousarray(p["coeffs"], np.float32)}
+            assert q["bonePresent"].shape == (bones,) and q["coeffCount"].shape == (bones, 6) and q["coeffs"].shape == (bones, 6, 17)
+            self.profiles.append(q)
+        self.profile_names = [p["name"] for p in self.profiles]
+
+    @property
+    def bone_count(self):
+        return len(self.names)
+
+    def profile_index(self, name):
+        return self.profile_names.index(name)
