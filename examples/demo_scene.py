@@ -14,9 +14,14 @@ and the fixed-step order of DemoScene.swift:56-75:
 and what the renderer does next with the skinned vertices (RayTracingScene.buildGeometryBuffers ->
 RTAccelerationBuilder.build, RTAccelerationBuilder.swift:75-185; raytraceKernel primary rays, RayTracing.metalinc:225-300):
 the player's acceleration structure is refitted behind the skinning of every step, its instance matrix is the entity's
-TransformComponent, and `--render` shoots a small image of primary rays at it and prints the depth as ASCII.
+TransformComponent. With `--render` the static items go the same way (include/sge_amd_ray_scene.h): the ground, the mirror's
+render mesh and the platform box are uploaded once as scene meshes (cachedStaticBLAS, RTAccelerationBuilder.swift:37-71), instanced
+with their model matrices (:168-185), the platforms' matrices are updated every step, and after the last step a small image of
+primary rays is shot at the whole scene, one shadow ray per hit towards a fixed sun (RayTracing.metalinc:319-338), and the depth
+is printed as ASCII with the shadowed pixels marked.
 
-Usage:  python examples/demo_scene.py [--steps 600] [--oracle] [--render]   (--oracle runs the CPU checker instead of the GPU)
+Usage:  python examples/demo_scene.py [--steps 600] [--oracle] [--render]   (--oracle runs the CPU checker instead of the GPU;
+the checker has no ray scene: `--oracle --render` shoots at the characters only)
 The player walks to the ground mover, rides it, then heads for the elevator.
 """
 import argparse
@@ -100,9 +105,43 @@ def build(engine):
     return ybot, world, platforms, service
 
 
-def render_probe(engine, width=56, height=28, fov_y=0.6):
+def vertex_normals(pos, idx):
+    """Area-weighted vertex normals of a static mesh (the demo's items carry none in the collision world)."""
+    tri = np.asarray(idx, np.int64).reshape(-1, 3)
+    p = np.asarray(pos, np.float64)
+    fn = np.cross(p[tri[:, 1]] - p[tri[:, 0]], p[tri[:, 2]] - p[tri[:, 0]])
+    n = np.zeros_like(p)
+    for k in range(3):
+        np.add.at(n, tri[:, k], fn)
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.where(length > 0, n / np.maximum(length, 1e-30), (0.0, 1.0, 0.0)).astype(np.float32)
+
+
+def entity_matrix(e):
+    return F.model_matrix({"translation": np.asarray(e["translation"], np.float32), "rotation": np.asarray(e["rotation"], np.float32),
+                           "scale": np.asarray(e["scale"], np.float32)})
+
+
+def scene_upload(engine, world):
+    """The static items of RayTracingScene.buildGeometryBuffers as scene meshes and instances: mesh 0 the ground plane, mesh 1 the
+    mirror's render mesh (placed like its hulls), mesh 2 the platform box, instanced twice. -> index of the first platform instance"""
+    z = np.load(os.path.join(sge.assets.GOLDEN_DIR, "ornate_mirror_static.npz"))
+    ground, hull, plats = world[0], world[1], [e for e in world if e.get("platform")]
+    for mesh, (pos, idx) in enumerate(((ground["positions"], ground["indices"]), (z["positions"], z["indices"]), (plats[0]["positions"], plats[0]["indices"]))):
+        pos = np.asarray(pos, np.float32).reshape(-1, 3)
+        engine.scene_mesh_upload(mesh, pos, vertex_normals(pos, idx), np.tile(np.array([1, 0, 0, 1], np.float32), (len(pos), 1)), idx)
+    items = [(0, ground), (1, hull)] + [(2, e) for e in plats]
+    engine.scene_instances([m for m, _ in items], np.stack([entity_matrix(e) for _, e in items]))
+    return 2
+
+
+SUN = np.array([0.35, 0.8, 0.45], np.float32) / np.linalg.norm(np.array([0.35, 0.8, 0.45], np.float32))   # L = normalize(-light.direction)
+
+
+def render_probe(engine, width=56, height=28, fov_y=0.6, scene=False):
     """Primary rays of the raytraceKernel (RayTracing.metalinc:225-235: origin = camera, direction through the pixel centre,
-    min_distance 0.001, max_distance 1e6) against the skinned items (here: the player) -> (hit mask, distances, hit records)."""
+    min_distance 0.001, max_distance 1e6) against the skinned items (here: the player) -> (hit mask, distances, hit records);
+    scene=True: against the whole ray scene, + the mask of hits whose shadow ray towards SUN is occluded or that face away from it."""
     b = engine.download(what=("bodies",))["bodies"]
     pos = b["position"][0].astype(np.float32)
     m = F.model_matrix({"translation": pos, "rotation": b["transformRotation"][0], "scale": np.ones(3, np.float32)})
@@ -116,26 +155,40 @@ def render_probe(engine, width=56, height=28, fov_y=0.6):
     th = np.tan(fov_y / 2)
     d = fwd + ((xs * 2 - 1) * th * width / height * 0.5)[..., None] * right + ((1 - ys * 2) * th)[..., None] * up
     d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).reshape(-1, 3).astype(np.float32)
+    if scene:
+        h = engine.scene_intersect(np.tile(eye, (len(d), 1)), d, -1)
+        hit = h["hit"] == 1
+        # RayTracing.metalinc:318-338: hitPos, bias = shadow_bias(distance) (:61), origin = hitPos + N * bias, min_distance = bias / 2
+        bias = np.maximum(np.float32(0.002), h["distance"] * np.float32(0.002)).astype(np.float32)
+        pos_hit = eye + d * h["distance"][:, None]
+        lit = hit & ((h["geomNormal"] * SUN).sum(1) > 0)      # NdotL <= 0: no light from the sun, no ray
+        occ = engine.scene_occluded(pos_hit + h["geomNormal"] * bias[:, None], np.tile(SUN, (len(d), 1)), -1, min_distance=bias * np.float32(0.5), max_distance=1e6)
+        shadow = hit & (~lit | (occ == 1))
+        return hit.reshape(height, width), h["distance"].reshape(height, width), h, shadow.reshape(height, width)
     h = engine.blas_intersect(np.tile(eye, (len(d), 1)), d, np.full(len(d), -1, np.int32))   # instance < 0: against every skinned item
     return h["hit"].reshape(height, width) == 1, h["distance"].reshape(height, width), h
 
 
-def ascii_depth(mask, dist):
+def ascii_depth(mask, dist, shadow=None):
+    """Depth as a ramp of characters; with `shadow`, shadowed pixels are drawn as 's'."""
     ramp = "@%#*+=-:."
     lo, hi = (dist[mask].min(), dist[mask].max()) if mask.any() else (0.0, 1.0)
     rows = []
     for r in range(mask.shape[0]):
-        rows.append("".join(ramp[min(len(ramp) - 1, int((dist[r, c] - lo) / max(hi - lo, 1e-6) * len(ramp)))] if mask[r, c] else " "
-                            for c in range(mask.shape[1])))
+        rows.append("".join(("s" if shadow is not None and shadow[r, c] else ramp[min(len(ramp) - 1, int((dist[r, c] - lo) / max(hi - lo, 1e-6) * len(ramp)))])
+                            if mask[r, c] else " " for c in range(mask.shape[1])))
     return "\n".join(rows)
 
 
-def run(engine, steps=600, dt=1.0 / 60.0, log=None):
+def run(engine, steps=600, dt=1.0 / 60.0, log=None, scene=False):
     ybot, world, platforms, service = build(engine)
+    first_platform = scene_upload(engine, world) if scene else 0
     trace = []
     for s in range(steps):
         for p in platforms:
             p.step(dt)                                  # KinematicPlatformMotionSystem
+        if scene:                                       # the instance descriptors of the moving items (RTAccelerationBuilder.swift:177)
+            engine.scene_instances_update(np.stack([entity_matrix(p.e) for p in platforms]), first=first_platform)
         service.update(world)                           # CollisionQueryRefreshSystem -> updateDynamicTransforms + refit
         service.upload_platforms(world)                 # the platform list KinematicMoveStopSystem reads
         pos = engine.download(what=("bodies",))["bodies"]["position"][0]
@@ -160,7 +213,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--oracle", action="store_true", help="run the CPU checker (tests/oracle_binding.py) instead of the GPU library")
-    ap.add_argument("--render", action="store_true", help="shoot primary rays at the player after the last step and print the depth image")
+    ap.add_argument("--render", action="store_true", help="shoot primary rays and shadow rays at the whole scene (ground, mirror, platforms, player) after the last step and "
+                    "print the depth image with shadowed pixels marked; with --oracle: primary rays at the characters only")
     args = ap.parse_args()
     if args.oracle:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -168,9 +222,16 @@ if __name__ == "__main__":
         eng = oracle_binding.oracle_engine()
     else:
         eng = sge.CharacterEngine(0)
-    trace, skinned = run(eng, args.steps, log=print)
+    scene = args.render and not args.oracle
+    trace, skinned = run(eng, args.steps, log=print, scene=scene)
     print("skinned vertices: %d, bounds %s .. %s" % (len(skinned), skinned.min(0).round(3), skinned.max(0).round(3)))
-    if args.render:
+    if scene:
+        mask, dist, hits, shadow = render_probe(eng, scene=True)
+        ids = hits["instance"][hits["hit"] == 1]
+        print("primary rays: %d of %d hit the scene (%d the player, %d static instances), %d shadowed, distances %.3f .. %.3f" % (
+            mask.sum(), mask.size, (ids < A.SCENE_STATIC_BASE).sum(), (ids >= A.SCENE_STATIC_BASE).sum(), shadow.sum(), dist[mask].min(), dist[mask].max()))
+        print(ascii_depth(mask, dist, shadow))
+    elif args.render:
         mask, dist, hits = render_probe(eng)
         print("primary rays: %d of %d hit the player, distances %.3f .. %.3f" % (mask.sum(), mask.size, dist[mask].min(), dist[mask].max()))
         print(ascii_depth(mask, dist))

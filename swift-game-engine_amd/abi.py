@@ -367,6 +367,30 @@ VARIANT_BLAS_PROTOTYPES = {
     "sge_blas_variant_buffers": (C.c_int, [VP, P(VP), P(VP), P(VP)]),
 }
 
+
+# include/sge_amd_ray_scene.h: static mesh instances and occlusion rays beside the crowd.
+class SceneInfo(C.Structure):
+    _fields_ = [("meshes", i32), ("staticInstances", i32), ("characters", i32), ("crowdReady", i32)]
+
+
+assert C.sizeof(SceneInfo) == 16
+SCENE_STATIC_BASE = 0x40000000  # scene id of static instance 0
+SGE_MAX_SCENE_MESHES = 64
+SGE_MAX_SCENE_INSTANCES = 262144
+
+SCENE_PROTOTYPES = {
+    "sge_scene_mesh_upload": (C.c_int, [VP, i32, VP, VP, VP, VP, i32, VP, i32]),
+    "sge_scene_mesh_info_get": (C.c_int, [VP, i32, P(BlasInfo)]),
+    "sge_scene_mesh_bounds_download": (C.c_int, [VP, i32, VP]),
+    "sge_scene_instances_set": (C.c_int, [VP, i32, VP, VP]),
+    "sge_scene_instances_update": (C.c_int, [VP, i32, i32, VP]),
+    "sge_scene_info_get": (C.c_int, [VP, P(SceneInfo)]),
+    "sge_scene_intersect_batch": (C.c_int, [VP, VP, i32, VP]),
+    "sge_scene_intersect_device": (C.c_int, [VP, VP, i32, VP]),
+    "sge_scene_occluded_batch": (C.c_int, [VP, VP, i32, VP]),
+    "sge_scene_occluded_device": (C.c_int, [VP, VP, i32, VP]),
+}
+
 LIB_NAME = "libsge_amd.so"
 
 
@@ -400,7 +424,7 @@ def load_library(path=None):
         raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = bind(C.CDLL(path))
-    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES):
+    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES):
         for name, (res, args) in table.items():  # (raises AttributeError if one is missing)
             fn = getattr(lib, name)
             fn.restype = res

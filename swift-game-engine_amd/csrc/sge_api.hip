@@ -159,6 +159,19 @@ struct sge_context {
     int varRowStride = 0, varBoundsChars = 0;
     DevVariantBlas hostVarBlasTable[SGE_MAX_MESH_VARIANTS] = {}; // what dVarBlasTable was last uploaded from (outlives the asynchronous copy)
     DevBuf dVarBlasTable, dVarBounds, dCharVariant, dVarBlasQueue;
+    // the ray scene (include/sge_amd_ray_scene.h): static meshes (RTAccelerationBuilder.swift:37-71), their instances (:168-185)
+    struct SceneMesh {
+        bool uploaded = false;
+        HostBlas host;
+        DevBuf entryLink, wideFirst, slotIdx, slotTri, boxes, pos, nrm, tan, uvs, indices;
+    } sceneMesh[SGE_MAX_SCENE_MESHES];
+    DevSceneMesh hostSceneTable[SGE_MAX_SCENE_MESHES] = {}; // what dSceneTable was last uploaded from
+    int sceneStatics = 0;
+    std::vector<int32_t> hostSceneMeshOf; // [sceneStatics]
+    DevBuf dSceneTable, dSceneMeshOf, dSceneMatrices, dSceneBoxes, dSceneOccluded;
+    // sge_scene_instances_update: the caller's matrices go through pinned memory, so that its array is free on return
+    struct SceneStage { void* host = nullptr; size_t bytes = 0; hipEvent_t copied = nullptr; bool inFlight = false; } sceneStage[2];
+    int sceneStageSlot = 0;
     // stats / profiling
     DevBuf dStats, dWaveProf, dOrderHist, dSepAgents, dSepCounts, dSepFlow;
     int separationIterations = 2; float separationMargin = 0.2f, separationHeightMargin = 0.1f; // AgentSeparationSystem.init :2146-2152
@@ -663,6 +676,75 @@ int buildInstanceLevel(sge_context* c, BlasTrace& T, const RaggedTrace* ragged =
     return SGE_OK;
 }
 
+// What a closest-hit launch over the crowd that shares one mesh reads: the context's own streams, boxes and matrices and, when a
+// ray may name no character, the instance level refreshed on the context's stream (sge_blas_intersect_*, sge_scene_*).
+int crowdTrace(sge_context* c, bool anyInstance, BlasTrace& T) {
+    T = BlasTrace{c->blas, c->dOutPos.p, c->dOutNrm.p, c->dOutTan.as<float>(), c->dBlasIndices.as<uint32_t>(), c->outLayoutAllocated,
+                  c->dBlasBounds.as<float>(), c->dBlasInstances.as<float>(), c->crowd.count, nullptr,
+                  c->blasHasUVs ? c->dBlasUVs.as<float>() : nullptr};
+    return anyInstance ? buildInstanceLevel(c, T) : SGE_OK;
+}
+
+// ---- the ray scene (include/sge_amd_ray_scene.h) ----
+// "The crowd is optional": one shared mesh with a structure, characters, and the buffers sge_blas_build / sge_characters_resize keep
+bool sceneCrowdReady(const sge_context* c) {
+    return c->extraVariants == 0 && c->mesh.vertexCount > 0 && c->blas.entryCount > 0 && c->crowd.count > 0 &&
+           c->blasBoundsChars == c->crowd.count && c->dBlasBounds.p && c->dBlasInstances.p && c->dOutPos.p && c->dOutNrm.p && c->dOutTan.p;
+}
+// the static half of a launch; S.crowd / S.T are filled by sceneTrace
+SceneTrace sceneStatics(sge_context* c) {
+    SceneTrace S{};
+    S.meshes = c->dSceneTable.as<DevSceneMesh>();
+    S.meshOf = c->dSceneMeshOf.as<int>();
+    S.matrices = c->dSceneMatrices.as<float>();
+    S.boxes = c->dSceneBoxes.as<float>();
+    S.statics = c->sceneStatics;
+    return S;
+}
+// + the crowd half with its instance level refreshed (whole-scene rays are always allowed)
+int sceneTrace(sge_context* c, SceneTrace& S) {
+    S = sceneStatics(c);
+    S.crowd = sceneCrowdReady(c) ? 1 : 0;
+    return S.crowd ? crowdTrace(c, true, S.T) : SGE_OK;
+}
+// the entry boxes of a static mesh by the structure's definition (include/sge_amd.h): a leaf entry's box is the min / max of the
+// vertices of its triangles, an inner entry's the union of its wide node's entries, the last row the union of the root's entries
+std::vector<float> sceneMeshBoxes(const HostBlas& h, const float* pos) {
+    const int E = h.entryCount();
+    std::vector<float> out((size_t)(E + 1) * 6);
+    for (int e = 0; e <= E; ++e)
+        for (int k = 0; k < 3; ++k) { out[(size_t)e * 6 + k] = kFloatMax; out[(size_t)e * 6 + 3 + k] = -kFloatMax; }
+    auto grow = [&](int row, const float* mn, const float* mx) {
+        for (int k = 0; k < 3; ++k) {
+            out[(size_t)row * 6 + k] = std::min(out[(size_t)row * 6 + k], mn[k]);
+            out[(size_t)row * 6 + 3 + k] = std::max(out[(size_t)row * 6 + 3 + k], mx[k]);
+        }
+    };
+    for (int e = 0; e < E; ++e) {
+        if (h.entryLink[(size_t)e * 2] >= 0) continue;
+        const int s0 = ~h.entryLink[(size_t)e * 2], cnt = h.entryLink[(size_t)e * 2 + 1];
+        for (int s = s0; s < s0 + cnt; ++s)
+            for (int k = 0; k < 3; ++k) { const float* p = pos + (size_t)h.slotIndices[(size_t)s * 3 + k] * 3; grow(e, p, p); }
+    }
+    for (int w = h.wideCount() - 1; w >= 0; --w) { // children are numbered after their parent
+        const int dst = h.wideParentEntry[w] < 0 ? E : h.wideParentEntry[w];
+        for (int e = h.wideFirst[w]; e < h.wideFirst[w + 1]; ++e) grow(dst, &out[(size_t)e * 6], &out[(size_t)e * 6 + 3]);
+    }
+    return out;
+}
+// mesh ids uploaded, every entry finite, 3x3 part invertible
+int checkSceneMatrices(const char* who, const float* m, int count) {
+    for (int i = 0; i < count; ++i) {
+        const float* a = m + (size_t)i * 16;
+        for (int k = 0; k < 16; ++k)
+            if (!std::isfinite(a[k])) { set_error(std::string(who) + ": a model matrix has a non-finite entry"); return SGE_ERR_INVALID; }
+        // the determinant as the kernels' inverse3 computes it (sge_blas_trace_dev.hpp)
+        const float det = dot(F3{a[0], a[1], a[2]}, cross(F3{a[4], a[5], a[6]}, F3{a[8], a[9], a[10]}));
+        if (!(det != 0.0f) || !std::isfinite(det) || !std::isfinite(1.0f / det)) { set_error(std::string(who) + ": the 3x3 part of a model matrix is not invertible"); return SGE_ERR_INVALID; }
+    }
+    return SGE_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -772,6 +854,10 @@ void sge_context_destroy(sge_context* c) {
     for (auto& vb : c->vblas)
         for (DevBuf* b : {&vb.entryLink, &vb.wideFirst, &vb.wideParent, &vb.wideLevel, &vb.slotIdx, &vb.slotTri, &vb.indices, &vb.tileStart, &vb.roundLen, &vb.roundCluster, &vb.roundIds, &vb.uvs}) b->release();
     for (DevBuf* b : {&c->dVarBlasTable, &c->dVarBounds, &c->dCharVariant, &c->dVarBlasQueue}) b->release();
+    for (auto& sm : c->sceneMesh)
+        for (DevBuf* b : {&sm.entryLink, &sm.wideFirst, &sm.slotIdx, &sm.slotTri, &sm.boxes, &sm.pos, &sm.nrm, &sm.tan, &sm.uvs, &sm.indices}) b->release();
+    for (DevBuf* b : {&c->dSceneTable, &c->dSceneMeshOf, &c->dSceneMatrices, &c->dSceneBoxes, &c->dSceneOccluded}) b->release();
+    for (auto& st : c->sceneStage) { if (st.host) (void)hipHostFree(st.host); if (st.copied) (void)hipEventDestroy(st.copied); }
     for (DevBuf* b : {&c->dVariantTable, &c->dVariantOf, &c->dVariantSnap[0], &c->dVariantSnap[1], &c->dVertexOff, &c->dVariantLists, &c->dSkinPlan}) b->release();
     for (hipEvent_t e : {c->evVariantSnap, c->evPlanDone[0], c->evPlanDone[1], c->variantStage[0].copied, c->variantStage[1].copied}) if (e) (void)hipEventDestroy(e);
     for (auto& st : c->variantStage) if (st.host) (void)hipHostFree(st.host);
@@ -2219,15 +2305,13 @@ int sge_blas_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t c
     if ((rc = c->dBlasHits.alloc((size_t)count * sizeof(sge_blas_hit))) != SGE_OK) return rc;
     bool anyInstance = false;
     for (int i = 0; i < count && !anyInstance; ++i) anyInstance = rays[i].instance < 0;
-    BlasTrace T{c->blas, c->dOutPos.p, c->dOutNrm.p, c->dOutTan.as<float>(), c->dBlasIndices.as<uint32_t>(), c->outLayoutAllocated,
-                c->dBlasBounds.as<float>(), c->dBlasInstances.as<float>(), c->crowd.count, nullptr,
-                c->blasHasUVs ? c->dBlasUVs.as<float>() : nullptr};
     if (ragged) {
         RaggedTrace R = variantTrace(c);
         if (anyInstance && (rc = buildInstanceLevel(c, R.T, &R)) != SGE_OK) return rc;
         launch_blas_intersect_ragged(R, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>(), anyInstance, c->stream);
     } else {
-        if (anyInstance && (rc = buildInstanceLevel(c, T)) != SGE_OK) return rc;
+        BlasTrace T{};
+        if ((rc = crowdTrace(c, anyInstance, T)) != SGE_OK) return rc;
         launch_blas_intersect(T, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>(), anyInstance, c->stream);
     }
     SGE_HIP(hipGetLastError());
@@ -2245,15 +2329,13 @@ int sge_blas_intersect_device(sge_context* c, const void* d_rays, int32_t count,
     (void)hipSetDevice(c->device);
     { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
     int rc;
-    BlasTrace T{c->blas, c->dOutPos.p, c->dOutNrm.p, c->dOutTan.as<float>(), c->dBlasIndices.as<uint32_t>(), c->outLayoutAllocated,
-                c->dBlasBounds.as<float>(), c->dBlasInstances.as<float>(), c->crowd.count, nullptr,
-                c->blasHasUVs ? c->dBlasUVs.as<float>() : nullptr};
     if (ragged) {
         RaggedTrace R = variantTrace(c);
         if (any_instance && (rc = buildInstanceLevel(c, R.T, &R)) != SGE_OK) return rc;
         launch_blas_intersect_ragged(R, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits), any_instance != 0, c->stream);
     } else {
-        if (any_instance && (rc = buildInstanceLevel(c, T)) != SGE_OK) return rc;
+        BlasTrace T{};
+        if ((rc = crowdTrace(c, any_instance != 0, T)) != SGE_OK) return rc;
         launch_blas_intersect(T, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits), any_instance != 0, c->stream);
     }
     SGE_HIP(hipGetLastError());
@@ -2356,6 +2438,200 @@ int sge_blas_variant_buffers(sge_context* c, void** d_bounds, void** d_char_vari
     if (d_char_variants) *d_char_variants = c->dCharVariant.p;
     if (d_indices)
         for (int v = 0; v < SGE_MAX_MESH_VARIANTS; ++v) d_indices[v] = v == 0 ? c->dBlasIndices.p : (v <= c->extraVariants ? c->vblas[v].indices.p : nullptr);
+    return SGE_OK;
+}
+
+// ---- the ray scene: static mesh instances and occlusion rays (include/sge_amd_ray_scene.h) ----
+int sge_scene_mesh_upload(sge_context* c, int32_t mesh, const float* positions, const float* normals, const float* tangents,
+                          const float* uvs, int32_t vertex_count, const uint32_t* indices, int32_t index_count) {
+    if (!c || !positions || !normals || !tangents || !indices || vertex_count <= 0 || index_count <= 0) { set_error("sge_scene_mesh_upload: bad argument"); return SGE_ERR_INVALID; }
+    if (mesh < 0 || mesh >= SGE_MAX_SCENE_MESHES) { set_error("sge_scene_mesh_upload: mesh id out of range (SGE_MAX_SCENE_MESHES)"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    std::string err;
+    HostBlas hb;
+    if (!hb.build(positions, vertex_count, indices, index_count, err)) { set_error(err); return SGE_ERR_INVALID; }
+    if (hb.levels * 63 + 1 > kBlasTraversalStackCap) { set_error("sge_scene_mesh_upload: hierarchy too deep for the closest-hit traversal stack"); return SGE_ERR_CAPACITY; }
+    const std::vector<float> boxes = sceneMeshBoxes(hb, positions);
+    sge_context::SceneMesh& sm = c->sceneMesh[mesh];
+    const size_t V = (size_t)vertex_count;
+    hipStream_t s = c->stream;
+    // into fresh buffers, swapped in on success: a failed upload leaves the mesh (and the table row instances name) as it was
+    DevBuf entryLink, wideFirst, slotIdx, slotTri, dBoxes, pos, nrm, tan, uv, idx;
+    int rc;
+    if ((rc = c->dSceneTable.alloc(sizeof(c->hostSceneTable))) != SGE_OK) return rc; // (fixed size: nothing below the swap allocates)
+    if ((rc = upload(entryLink, hb.entryLink.data(), hb.entryLink.size() * 4, s)) != SGE_OK ||
+        (rc = upload(wideFirst, hb.wideFirst.data(), hb.wideFirst.size() * 4, s)) != SGE_OK ||
+        (rc = upload(slotIdx, hb.slotIndices.data(), hb.slotIndices.size() * 4, s)) != SGE_OK ||
+        (rc = upload(slotTri, hb.slotTriangle.data(), hb.slotTriangle.size() * 4, s)) != SGE_OK ||
+        (rc = upload(dBoxes, boxes.data(), boxes.size() * 4, s)) != SGE_OK ||
+        (rc = upload(pos, positions, V * 12, s)) != SGE_OK ||
+        (rc = upload(nrm, normals, V * 12, s)) != SGE_OK ||
+        (rc = upload(tan, tangents, V * 16, s)) != SGE_OK ||
+        (uvs && (rc = upload(uv, uvs, V * 8, s)) != SGE_OK) ||
+        (rc = upload(idx, indices, (size_t)index_count * 4, s)) != SGE_OK) {
+        (void)hipStreamSynchronize(s); // copies from the caller's arrays may be pending
+        for (DevBuf* b : {&entryLink, &wideFirst, &slotIdx, &slotTri, &dBoxes, &pos, &nrm, &tan, &uv, &idx}) b->release();
+        return rc;
+    }
+    SGE_HIP(hipStreamSynchronize(s));
+    for (DevBuf* b : {&sm.entryLink, &sm.wideFirst, &sm.slotIdx, &sm.slotTri, &sm.boxes, &sm.pos, &sm.nrm, &sm.tan, &sm.uvs, &sm.indices}) b->release();
+    sm.entryLink = entryLink; sm.wideFirst = wideFirst; sm.slotIdx = slotIdx; sm.slotTri = slotTri; sm.boxes = dBoxes;
+    sm.pos = pos; sm.nrm = nrm; sm.tan = tan; sm.uvs = uv; sm.indices = idx;
+    sm.host = std::move(hb);
+    sm.uploaded = true;
+    const HostBlas& h = sm.host;
+    c->hostSceneTable[mesh] = DevSceneMesh{h.entryCount(), h.vertexCount, h.triCount, 0, sm.wideFirst.as<int>(), sm.entryLink.as<int2>(),
+                                           sm.slotIdx.as<uint32_t>(), sm.slotTri.as<uint32_t>(), sm.boxes.as<float>(), sm.pos.as<float>(),
+                                           sm.nrm.as<float>(), sm.tan.as<float>(), uvs ? sm.uvs.as<float>() : nullptr, sm.indices.as<uint32_t>()};
+    if ((rc = upload(c->dSceneTable, c->hostSceneTable, sizeof(c->hostSceneTable), s)) != SGE_OK) return rc;
+    // instances that name this mesh: their world boxes follow the new root box
+    if (c->sceneStatics > 0) launch_scene_instance_boxes(sceneStatics(c), 0, (c->sceneStatics + 63) / 64, s);
+    SGE_HIP(hipGetLastError());
+    SGE_HIP(hipStreamSynchronize(s));
+    return SGE_OK;
+}
+
+int sge_scene_mesh_info_get(sge_context* c, int32_t mesh, sge_blas_info* info) {
+    if (!c || !info) { set_error("sge_scene_mesh_info_get: bad argument"); return SGE_ERR_INVALID; }
+    if (mesh < 0 || mesh >= SGE_MAX_SCENE_MESHES || !c->sceneMesh[mesh].uploaded) { set_error("sge_scene_mesh_info_get: scene mesh was never uploaded"); return SGE_ERR_INVALID; }
+    const HostBlas& h = c->sceneMesh[mesh].host;
+    *info = sge_blas_info{h.triCount, h.clusterCount, h.entryCount(), h.wideCount(), h.levels, (int32_t)h.vertexEntries.size()};
+    return SGE_OK;
+}
+
+int sge_scene_mesh_bounds_download(sge_context* c, int32_t mesh, float* bounds) {
+    if (!c || !bounds) { set_error("sge_scene_mesh_bounds_download: bad argument"); return SGE_ERR_INVALID; }
+    if (mesh < 0 || mesh >= SGE_MAX_SCENE_MESHES || !c->sceneMesh[mesh].uploaded) { set_error("sge_scene_mesh_bounds_download: scene mesh was never uploaded"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    SGE_HIP(hipMemcpy(bounds, c->sceneMesh[mesh].boxes.p, (size_t)(c->sceneMesh[mesh].host.entryCount() + 1) * 24, hipMemcpyDeviceToHost));
+    return SGE_OK;
+}
+
+int sge_scene_instances_set(sge_context* c, int32_t count, const int32_t* mesh_of_instance, const float* model_matrices) {
+    if (!c || count < 0 || (count > 0 && (!mesh_of_instance || !model_matrices))) { set_error("sge_scene_instances_set: bad argument"); return SGE_ERR_INVALID; }
+    if (count > SGE_MAX_SCENE_INSTANCES) { set_error("sge_scene_instances_set: more than SGE_MAX_SCENE_INSTANCES static instances"); return SGE_ERR_INVALID; }
+    for (int i = 0; i < count; ++i) {
+        const int m = mesh_of_instance[i];
+        if (m < 0 || m >= SGE_MAX_SCENE_MESHES || !c->sceneMesh[m].uploaded) { set_error("sge_scene_instances_set: an instance names a scene mesh that was never uploaded"); return SGE_ERR_INVALID; }
+    }
+    { int rcm = checkSceneMatrices("sge_scene_instances_set", model_matrices, count); if (rcm != SGE_OK) return rcm; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    if (count == 0) { c->sceneStatics = 0; c->hostSceneMeshOf.clear(); return SGE_OK; }
+    // new buffers first: a failed allocation leaves the list in place
+    DevBuf meshOf, matrices, boxes;
+    int rc;
+    if ((rc = upload(meshOf, mesh_of_instance, (size_t)count * 4, c->stream)) != SGE_OK ||
+        (rc = upload(matrices, model_matrices, (size_t)count * 64, c->stream)) != SGE_OK ||
+        (rc = boxes.alloc(((size_t)count + (count + 63) / 64) * 24)) != SGE_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        meshOf.release(); matrices.release(); boxes.release();
+        return rc;
+    }
+    c->dSceneMeshOf.release(); c->dSceneMatrices.release(); c->dSceneBoxes.release();
+    c->dSceneMeshOf = meshOf; c->dSceneMatrices = matrices; c->dSceneBoxes = boxes;
+    c->sceneStatics = count;
+    c->hostSceneMeshOf.assign(mesh_of_instance, mesh_of_instance + count);
+    launch_scene_instance_boxes(sceneStatics(c), 0, (count + 63) / 64, c->stream);
+    SGE_HIP(hipGetLastError());
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    return SGE_OK;
+}
+
+int sge_scene_instances_update(sge_context* c, int32_t first, int32_t count, const float* model_matrices) {
+    if (!c || first < 0 || count < 0 || (count > 0 && !model_matrices)) { set_error("sge_scene_instances_update: bad argument"); return SGE_ERR_INVALID; }
+    if ((long long)first + count > c->sceneStatics) { set_error("sge_scene_instances_update: instance range out of range"); return SGE_ERR_INVALID; }
+    { int rcm = checkSceneMatrices("sge_scene_instances_update", model_matrices, count); if (rcm != SGE_OK) return rcm; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    const size_t bytes = (size_t)count * 64;
+    // two pinned staging slots taken in turn (as variantStage): the host waits only for the copy of the update before last
+    sge_context::SceneStage& st = c->sceneStage[c->sceneStageSlot];
+    c->sceneStageSlot ^= 1;
+    if (st.inFlight) { SGE_HIP(hipEventSynchronize(st.copied)); st.inFlight = false; }
+    if (!st.copied) SGE_HIP(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    if (bytes > st.bytes) {
+        if (st.host) { (void)hipHostFree(st.host); st.host = nullptr; st.bytes = 0; }
+        SGE_HIP(hipHostMalloc(&st.host, bytes, hipHostMallocDefault));
+        st.bytes = bytes;
+    }
+    memcpy(st.host, model_matrices, bytes);
+    SGE_HIP(hipMemcpyAsync(c->dSceneMatrices.as<float>() + (size_t)first * 16, st.host, bytes, hipMemcpyHostToDevice, c->stream));
+    SGE_HIP(hipEventRecord(st.copied, c->stream));
+    st.inFlight = true;
+    const int g0 = first / 64, g1 = (first + count - 1) / 64;
+    launch_scene_instance_boxes(sceneStatics(c), g0, g1 - g0 + 1, c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+
+int sge_scene_info_get(sge_context* c, struct sge_scene_info* info) {
+    if (!c || !info) { set_error("sge_scene_info_get: bad argument"); return SGE_ERR_INVALID; }
+    int meshes = 0;
+    for (const auto& sm : c->sceneMesh) meshes += sm.uploaded ? 1 : 0;
+    *info = sge_scene_info{meshes, c->sceneStatics, c->crowd.count, sceneCrowdReady(c) ? 1 : 0};
+    return SGE_OK;
+}
+
+int sge_scene_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t count, sge_blas_hit* hits) {
+    if (!c || count < 0 || (count > 0 && (!rays || !hits))) { set_error("sge_scene_intersect_batch: bad argument"); return SGE_ERR_INVALID; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    int rc;
+    if ((rc = upload(c->dBlasRays, rays, (size_t)count * sizeof(sge_blas_ray), c->stream)) != SGE_OK) return rc;
+    if ((rc = c->dBlasHits.alloc((size_t)count * sizeof(sge_blas_hit))) != SGE_OK) return rc;
+    SceneTrace S;
+    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
+    launch_scene_trace(S, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>(), c->stream);
+    SGE_HIP(hipGetLastError());
+    SGE_HIP(hipMemcpyAsync(hits, c->dBlasHits.p, (size_t)count * sizeof(sge_blas_hit), hipMemcpyDeviceToHost, c->stream));
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    return SGE_OK;
+}
+
+int sge_scene_intersect_device(sge_context* c, const void* d_rays, int32_t count, void* d_hits) {
+    if (!c || count < 0 || (count > 0 && (!d_rays || !d_hits))) { set_error("sge_scene_intersect_device: bad argument"); return SGE_ERR_INVALID; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
+    int rc;
+    SceneTrace S;
+    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
+    launch_scene_trace(S, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits), c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+
+int sge_scene_occluded_batch(sge_context* c, const sge_blas_ray* rays, int32_t count, int32_t* occluded) {
+    if (!c || count < 0 || (count > 0 && (!rays || !occluded))) { set_error("sge_scene_occluded_batch: bad argument"); return SGE_ERR_INVALID; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    int rc;
+    if ((rc = upload(c->dBlasRays, rays, (size_t)count * sizeof(sge_blas_ray), c->stream)) != SGE_OK) return rc;
+    if ((rc = c->dSceneOccluded.alloc((size_t)count * sizeof(int32_t))) != SGE_OK) return rc;
+    SceneTrace S;
+    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
+    launch_scene_occlusion(S, c->dBlasRays.as<sge_blas_ray>(), count, c->dSceneOccluded.as<int32_t>(), c->stream);
+    SGE_HIP(hipGetLastError());
+    SGE_HIP(hipMemcpyAsync(occluded, c->dSceneOccluded.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    return SGE_OK;
+}
+
+int sge_scene_occluded_device(sge_context* c, const void* d_rays, int32_t count, void* d_occluded) {
+    if (!c || count < 0 || (count > 0 && (!d_rays || !d_occluded))) { set_error("sge_scene_occluded_device: bad argument"); return SGE_ERR_INVALID; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
+    int rc;
+    SceneTrace S;
+    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
+    launch_scene_occlusion(S, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<int32_t*>(d_occluded), c->stream);
+    SGE_HIP(hipGetLastError());
     return SGE_OK;
 }
 

@@ -258,170 +258,30 @@ __global__ __launch_bounds__(kWave) void blas_intersect_kernel(BlasTrace T, cons
     const F3 wo{R.origin[0], R.origin[1], R.origin[2]}, wd{R.direction[0], R.direction[1], R.direction[2]};
     const float tMin = smax(R.minDistance, 0.0f);
 
-    float bestT = R.maxDistance, bestU = 0, bestV = 0;
-    uint32_t bestPrim = 0;
-    int bestInst = -1;
+    BlasBest best{R.maxDistance, 0, 0, 0u, -1};
 
-    // closest hit inside one character; accepted when closer than bestT (equal: only the first character found keeps it)
+    // closest hit inside one character (blasTraverseClosest: accepted when closer than best.t; equal: the smaller index keeps it)
     auto traverse = [&](int inst) {
-        const Aff M = loadInstance(T.instances, inst);
-        const Inv3 Mi = inverse3(M);
-        const F3 o = mul3(Mi, wo - M.c3), d = mul3(Mi, wd);
-        const F3 inv = invDir(d);
-        const float* P = reinterpret_cast<const float*>(T.positions) + (size_t)inst * B.vertexCount * STRIDE;
-        const float* boxes = T.bounds + (size_t)inst * (B.entryCount + 1) * 6;
-        // (distance bits, primitive id); distances are >= 0, so their bit patterns order like the values. A character found
-        // earlier keeps a tie: the starting key carries primitive 0, which nothing is smaller than at equal distance.
-        // (with the instances visited in grid order rather than index order, a character with a smaller index than the holder of
-        // the best hit so far may still take it at equal distance: its starting key accepts any primitive there)
-        unsigned long long best = ((unsigned long long)__float_as_uint(bestT) << 32) | ((bestInst < 0 || inst < bestInst) ? 0xffffffffull : 0ull);
-        float u0 = 0, v0 = 0;
-        bool found = false;
-        int sp = 1;
-        if (lane == 0) stack[0] = 0;
-        __syncthreads();
-        while (sp > 0) {
-            const int w = stack[sp - 1];
-            --sp;
-            __syncthreads();
-            const int first = B.wideFirst[w], cnt = B.wideFirst[w + 1] - first;
-            bool pass = false;
-            int2 link = make_int2(0, 0);
-            if (lane < cnt) {
-                link = B.entryLink[first + lane];
-                pass = slabPass(boxes + (size_t)(first + lane) * 6, o, inv, tMin, __uint_as_float((unsigned)(best >> 32)));
-            }
-            const unsigned long long inner = __ballot(pass && link.x >= 0), leaves = __ballot(pass && link.x < 0);
-            if (pass && link.x >= 0) {
-                const int at = sp + __popcll(inner & ((1ull << lane) - 1));
-                if (at < kBlasStack) stack[at] = link.x;
-            }
-            sp = min(sp + __popcll(inner), kBlasStack);
-            unsigned long long m = leaves;
-            while (m) {
-                const int src = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const int firstSlot = ~__shfl(link.x, src, kWave), count = __shfl(link.y, src, kWave);
-                unsigned long long key = ~0ull;
-                float u = 0, v = 0;
-                if (lane < count) {
-                    const uint32_t* ix = B.slotIndices + (size_t)(firstSlot + lane) * 3;
-                    const F3 p0 = loadP<STRIDE>(P, ix[0]), p1 = loadP<STRIDE>(P, ix[1]), p2 = loadP<STRIDE>(P, ix[2]);
-                    float t;
-                    if (rayTriangleUV(o, d, p0, p1, p2, 1e-6f, t, u, v) && t >= tMin && t <= R.maxDistance)
-                        key = ((unsigned long long)__float_as_uint(t) << 32) | B.slotTriangle[firstSlot + lane];
-                }
-                unsigned long long k = key;
-                for (int off = 32; off > 0; off >>= 1) {
-                    const unsigned lo32 = __shfl_xor((unsigned)k, off, kWave), hi32 = __shfl_xor((unsigned)(k >> 32), off, kWave);
-                    const unsigned long long other = ((unsigned long long)hi32 << 32) | lo32;
-                    k = other < k ? other : k;
-                }
-                if (k != ~0ull && k < best) {
-                    best = k;
-                    found = true;
-                    const int winner = __ffsll((long long)__ballot(key == k)) - 1;
-                    u0 = __shfl(u, winner, kWave);
-                    v0 = __shfl(v, winner, kWave);
-                }
-            }
-            __syncthreads();
-        }
-        if (found) {
-            bestT = __uint_as_float((unsigned)(best >> 32));
-            bestPrim = (uint32_t)best;
-            bestU = u0; bestV = v0;
-            bestInst = inst;
-        }
+        const BlasTreeRef G{B.wideFirst, B.entryLink, B.slotIndices, B.slotTriangle, T.bounds + (size_t)inst * (B.entryCount + 1) * 6,
+                            reinterpret_cast<const float*>(T.positions) + (size_t)inst * B.vertexCount * STRIDE};
+        blasTraverseClosest<STRIDE>(stack, lane, G, loadInstance(T.instances, inst), wo, wd, tMin, R.maxDistance, inst, best);
+        return false;
     };
 
     if (R.instance >= 0) {
         traverse(R.instance);
     } else if (T.worldBoxesValid && T.instOrder) {
-        // three scans of 64 boxes: super-groups (4,096 instances each: 62 of them hold 250,000 characters, one step), the groups of
-        // the ones the ray may hit, the instances of those groups — grouped by where they ARE (grid order), not by their index
-        const F3 inv = invDir(wd);
-        const int groups = (T.chars + kWave - 1) / kWave, supers = (groups + kWave - 1) / kWave;
-        for (int sbase = 0; sbase < supers; sbase += kWave) {
-            const int sg = sbase + lane;
-            unsigned long long sm = __ballot(sg < supers && slabPass(T.superBoxes + (size_t)sg * 6, wo, inv, tMin, bestT));
-            while (sm) {
-                const int ssrc = __ffsll((long long)sm) - 1;
-                sm &= sm - 1;
-                const int g = (sbase + ssrc) * kWave + lane;
-                unsigned long long gm = __ballot(g < groups && slabPass(T.groupBoxes + (size_t)g * 6, wo, inv, tMin, bestT));
-                while (gm) {
-                    const int gsrc = __ffsll((long long)gm) - 1;
-                    gm &= gm - 1;
-                    const int slot = ((sbase + ssrc) * kWave + gsrc) * kWave + lane;
-                    const int inst = slot < T.chars ? T.instOrder[slot] : -1;
-                    const bool pass = inst >= 0 && slabPass(T.worldBoxes + (size_t)inst * 6, wo, inv, tMin, bestT);
-                    unsigned long long m = __ballot(pass);
-                    while (m) {
-                        const int src = __ffsll((long long)m) - 1;
-                        m &= m - 1;
-                        traverse(__shfl(inst, src, kWave));
-                    }
-                }
-            }
-        }
+        blasScanGrid(T, lane, wo, invDir(wd), tMin, best.t, traverse);
     } else if (T.worldBoxesValid) {
-        const F3 inv = invDir(wd);
-        const int groups = (T.chars + kWave - 1) / kWave;
-        const float* groupBoxes = T.worldBoxes + (size_t)T.chars * 6;
-        for (int gbase = 0; gbase < groups; gbase += kWave) {
-            const int g = gbase + lane;
-            unsigned long long gm = __ballot(g < groups && slabPass(groupBoxes + (size_t)g * 6, wo, inv, tMin, bestT));
-            while (gm) {
-                const int gsrc = __ffsll((long long)gm) - 1;
-                gm &= gm - 1;
-                const int base = (gbase + gsrc) * kWave, i = base + lane;
-                const bool pass = i < T.chars && slabPass(T.worldBoxes + (size_t)i * 6, wo, inv, tMin, bestT);
-                unsigned long long m = __ballot(pass);
-                while (m) {
-                    const int src = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    traverse(base + src);
-                }
-            }
-        }
+        blasScanFlat(T.worldBoxes, T.chars, lane, wo, invDir(wd), tMin, best.t, traverse);
     }
     if (lane != 0) return;
-    if (bestInst >= 0) {
-        const Aff M = loadInstance(T.instances, bestInst);
-        const size_t vbase = (size_t)bestInst * B.vertexCount;
-        const float* P = reinterpret_cast<const float*>(T.positions) + vbase * STRIDE;
-        const uint32_t* ix = T.indices + (size_t)bestPrim * 3;
-        const uint32_t i0 = ix[0], i1 = ix[1], i2 = ix[2];
-        // RayTracing.metalinc:258-268
-        const F3 w0 = affMulPoint(M, loadP<STRIDE>(P, i0)), w1 = affMulPoint(M, loadP<STRIDE>(P, i1)), w2 = affMulPoint(M, loadP<STRIDE>(P, i2));
-        F3 N = normalize(cross(w1 - w0, w2 - w0));
-        if (dot(N, wd) > 0.0f) N = -N;
-        // :283-300
-        const float* NB = reinterpret_cast<const float*>(T.normals) + vbase * STRIDE;
-        const float* TB = T.tangents + vbase * 4;
-        const float bx = bestU, by = bestV, bw = 1.0f - bx - by;
-        const F3 n0 = loadP<STRIDE>(NB, i0), n1 = loadP<STRIDE>(NB, i1), n2 = loadP<STRIDE>(NB, i2);
-        const float* q0 = TB + (size_t)i0 * 4; const float* q1 = TB + (size_t)i1 * 4; const float* q2 = TB + (size_t)i2 * 4;
-        const F3 nObj = normalize((n0 * bw + n1 * bx) + n2 * by);
-        float t4[4];
-        for (int k = 0; k < 4; ++k) t4[k] = (q0[k] * bw + q1[k] * bx) + q2[k] * by;
-        const float r4 = 1.0f / sqrtf(((t4[0] * t4[0] + t4[1] * t4[1]) + t4[2] * t4[2]) + t4[3] * t4[3]);
-        const F3 tObj = normalize(F3{t4[0] * r4, t4[1] * r4, t4[2] * r4});
-        const float tw = t4[3] * r4;
-        const F3 nW = normalize((M.c0 * nObj.x + M.c1 * nObj.y) + M.c2 * nObj.z);
-        const F3 tW = normalize((M.c0 * tObj.x + M.c1 * tObj.y) + M.c2 * tObj.z);
-        const F3 bW = normalize(cross(nW, tW) * tw);
-        H.hit = 1; H.primitive = (int32_t)bestPrim; H.instance = bestInst; H.distance = bestT; H.bary[0] = bx; H.bary[1] = by;
-        H.geomNormal[0] = N.x; H.geomNormal[1] = N.y; H.geomNormal[2] = N.z;
-        H.normal[0] = nW.x; H.normal[1] = nW.y; H.normal[2] = nW.z;
-        H.tangent[0] = tW.x; H.tangent[1] = tW.y; H.tangent[2] = tW.z;
-        H.bitangent[0] = bW.x; H.bitangent[1] = bW.y; H.bitangent[2] = bW.z;
-        if (T.uvs) { // interp_uv, RayTracing.metalinc:106-119
-            const float* a0 = T.uvs + (size_t)i0 * 2; const float* a1 = T.uvs + (size_t)i1 * 2; const float* a2 = T.uvs + (size_t)i2 * 2;
-            H.uv[0] = (a0[0] * bw + a1[0] * bx) + a2[0] * by;
-            H.uv[1] = (a0[1] * bw + a1[1] * bx) + a2[1] * by;
-        }
+    if (best.inst >= 0) {
+        const size_t vbase = (size_t)best.inst * B.vertexCount;
+        blasHitRecord<STRIDE>(loadInstance(T.instances, best.inst), reinterpret_cast<const float*>(T.positions) + vbase * STRIDE,
+                              reinterpret_cast<const float*>(T.normals) + vbase * STRIDE, T.tangents + vbase * 4, T.uvs,
+                              T.indices + (size_t)best.prim * 3, wd, best, H);
+        H.instance = best.inst;
     }
     hits[blockIdx.x] = H;
 }

@@ -7,6 +7,7 @@
 #include "../../include/sge_amd.h"
 #include "../../include/sge_amd_variants.h"
 #include "../../include/sge_amd_variant_blas.h"
+#include "../../include/sge_amd_ray_scene.h"
 #include "sge_math.hpp"
 
 namespace sge {
@@ -25,6 +26,7 @@ static_assert(sizeof(sge_bvh_node) == 44, "layout");
 static_assert(sizeof(sge_tick_desc) == 32, "layout");
 static_assert(sizeof(sge_skin_plan_info) == 64, "layout");
 static_assert(sizeof(struct sge_blas_variant_layout) == 48, "layout");
+static_assert(sizeof(struct sge_scene_info) == 16, "layout");
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
@@ -455,5 +457,29 @@ struct RaggedTrace {
 };
 void launch_blas_world_boxes_ragged(const RaggedTrace& R, float* worldBoxes, hipStream_t s);
 void launch_blas_intersect_ragged(RaggedTrace R, const sge_blas_ray* d_rays, int n, sge_blas_hit* d_hits, bool anyInstance, hipStream_t s);
+
+// ---- the ray scene: static mesh instances beside the crowd (include/sge_amd_ray_scene.h, sge_ray_scene.hip) ---- //
+// One row per static mesh, in device memory: the topology of HostBlas::build, the entry boxes (object space, computed once on the
+// host) and the mesh's own streams, positions and normals packed (three floats per vertex).
+struct DevSceneMesh {
+    int entryCount, vertexCount, triCount, _pad;
+    const int* wideFirst; const int2* entryLink; const uint32_t* slotIndices; const uint32_t* slotTriangle;
+    const float* boxes;      // [entryCount + 1][6]
+    const float* positions; const float* normals; const float* tangents; const float* uvs; // uvs: or null
+    const uint32_t* indices; // [T][3] in primitive order
+};
+struct SceneTrace {
+    const DevSceneMesh* meshes; // device [SGE_MAX_SCENE_MESHES]
+    const int* meshOf;          // [statics]
+    const float* matrices;      // [statics][16] model matrices, column-major
+    float* boxes;               // [statics + ceil(statics / 64)][6]: world box per instance, then per 64 consecutive instances
+    int statics;
+    int crowd;                  // 1: T describes a crowd to trace, its instance level refreshed by the caller on the same stream
+    BlasTrace T;
+};
+// world boxes of the instances of groups [firstGroup, firstGroup + groups) (64 consecutive instances each) and the groups' boxes
+void launch_scene_instance_boxes(const SceneTrace& S, int firstGroup, int groups, hipStream_t s);
+void launch_scene_trace(const SceneTrace& S, const sge_blas_ray* d_rays, int n, sge_blas_hit* d_hits, hipStream_t s);
+void launch_scene_occlusion(const SceneTrace& S, const sge_blas_ray* d_rays, int n, int32_t* d_occluded, hipStream_t s);
 
 } // namespace sge

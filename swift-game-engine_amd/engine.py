@@ -544,6 +544,81 @@ class CharacterEngine:
         self._call("blas_variant_bounds_download", first, count, ptr(bounds), ptr(variants))
         return bounds, variants
 
+    # -- the ray scene: static mesh instances and occlusion rays (include/sge_amd_ray_scene.h; product only) -- #
+    def scene_mesh_upload(self, mesh, positions, normals, tangents, indices, uvs=None):
+        """encoder.build for one static slice (RTAccelerationBuilder.swift:37-71) -> abi.BlasInfo."""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(tangents, np.float32).reshape(-1, 4)
+        u = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        if n.shape[0] != p.shape[0] or t.shape[0] != p.shape[0] or (u is not None and u.shape[0] != p.shape[0]):
+            raise SgeError("scene_mesh_upload: the streams differ in vertex count")
+        self._call("scene_mesh_upload", int(mesh), ptr(p), ptr(n), ptr(t), ptr(u), p.shape[0], ptr(idx), idx.shape[0])
+        return self.scene_mesh_info(mesh)
+
+    def scene_mesh_info(self, mesh):
+        info = abi.BlasInfo()
+        self._call("scene_mesh_info_get", int(mesh), C.byref(info))
+        return info
+
+    def scene_mesh_bounds(self, mesh):
+        out = np.zeros((self.scene_mesh_info(mesh).entryCount + 1, 6), np.float32)
+        self._call("scene_mesh_bounds_download", int(mesh), ptr(out))
+        return out
+
+    def scene_instances(self, mesh_of_instance, model_matrices):
+        """Replaces the static instance list: mesh ids [S] and column-major matrices [S][16] (item.modelMatrix)."""
+        ids = np.ascontiguousarray(mesh_of_instance, np.int32).reshape(-1)
+        m = np.ascontiguousarray(model_matrices, np.float32).reshape(-1, 16)
+        if m.shape[0] != ids.shape[0]:
+            raise SgeError("scene_instances: one matrix per instance")
+        self._call("scene_instances_set", ids.shape[0], ptr(ids), ptr(m))
+
+    def scene_instances_update(self, model_matrices, first=0):
+        """New matrices for instances [first, first + len); enqueued on the context's stream."""
+        m = np.ascontiguousarray(model_matrices, np.float32).reshape(-1, 16)
+        self._call("scene_instances_update", int(first), m.shape[0], ptr(m))
+
+    def scene_info(self):
+        info = abi.SceneInfo()
+        self._call("scene_info_get", C.byref(info))
+        return info
+
+    @staticmethod
+    def _scene_rays(origins, directions, instances, min_distance, max_distance):
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        r = np.zeros(o.shape[0], abi.blas_ray_dtype)
+        r["origin"] = o
+        r["direction"] = np.asarray(directions, np.float32).reshape(-1, 3)
+        r["minDistance"] = min_distance
+        r["maxDistance"] = max_distance
+        r["instance"] = instances
+        return r
+
+    def scene_intersect(self, origins, directions, instances=-1, min_distance=0.001, max_distance=1e6):
+        """Closest hit over the scene -> blas_hit_dtype. `instances`: scene ids (character c = c, static instance s =
+        abi.SCENE_STATIC_BASE + s), < 0 = the whole scene. Array conventions of blas_intersect."""
+        r = self._scene_rays(origins, directions, instances, min_distance, max_distance)
+        out = np.zeros(r.shape[0], abi.blas_hit_dtype)
+        self._call("scene_intersect_batch", ptr(r), r.shape[0], ptr(out))
+        return out
+
+    def scene_occluded(self, origins, directions, instances=-1, min_distance=0.001, max_distance=1e6):
+        """The shadow ray's question -> int32 [n]: 1 when anything is hit within [min_distance, max_distance]."""
+        r = self._scene_rays(origins, directions, instances, min_distance, max_distance)
+        out = np.zeros(r.shape[0], np.int32)
+        self._call("scene_occluded_batch", ptr(r), r.shape[0], ptr(out))
+        return out
+
+    def scene_intersect_device(self, d_rays, count, d_hits):
+        """Rays / hits already in device memory (blas_ray_dtype / blas_hit_dtype records); asynchronous on the context's stream."""
+        self._call("scene_intersect_device", C.c_void_p(d_rays), int(count), C.c_void_p(d_hits))
+
+    def scene_occluded_device(self, d_rays, count, d_occluded):
+        """Rays and int32 words already in device memory; asynchronous on the context's stream."""
+        self._call("scene_occluded_device", C.c_void_p(d_rays), int(count), C.c_void_p(d_occluded))
+
     def blas_profile(self, reset=True):
         ms, n = C.c_double(0), C.c_int64(0)
         self._call("blas_profile_read", C.byref(ms), C.byref(n), int(reset))
