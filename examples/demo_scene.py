@@ -131,6 +131,7 @@ def scene_upload(engine, world):
         pos = np.asarray(pos, np.float32).reshape(-1, 3)
         engine.scene_mesh_upload(mesh, pos, vertex_normals(pos, idx), np.tile(np.array([1, 0, 0, 1], np.float32), (len(pos), 1)), idx)
     items = [(0, ground), (1, hull)] + [(2, e) for e in plats]
+    scene_upload.items = [(z["positions"] if m == 1 else e["positions"], e) for m, e in items]   # what shaded_image frames
     engine.scene_instances([m for m, _ in items], np.stack([entity_matrix(e) for _, e in items]))
     return 2
 
@@ -167,6 +168,55 @@ def render_probe(engine, width=56, height=28, fov_y=0.6, scene=False):
         return hit.reshape(height, width), h["distance"].reshape(height, width), h, shadow.reshape(height, width)
     h = engine.blas_intersect(np.tile(eye, (len(d), 1)), d, np.full(len(d), -1, np.int32))   # instance < 0: against every skinned item
     return h["hit"].reshape(height, width) == 1, h["distance"].reshape(height, width), h
+
+
+def shaded_image(engine, path, width=320, height=200, fov_y=0.9):
+    """The shaded frame (include/sge_amd_render.h: raytraceKernel's layers, lights and bounces in one launch) as a binary PPM, from a
+    camera of its own that is pulled back until the mirror (a smooth metal: the mirror path), both platforms and the player are in
+    view above the ground. -> the AOV records"""
+    b = engine.download(what=("bodies",))["bodies"]
+    pos = b["position"][0].astype(np.float64)
+    m = F.model_matrix({"translation": pos.astype(np.float32), "rotation": b["transformRotation"][0], "scale": np.ones(3, np.float32)})
+    engine.blas_instances(np.asarray(m, np.float32).reshape(1, 16))
+    # the world-space centres of the mirror and the platforms (instances 1 ..; a matrix is stored by column), and the player
+    points = [pos + (0.0, 1.0, 0.0)]
+    for p, e in scene_upload.items[1:]:
+        M = np.asarray(entity_matrix(e), np.float64).reshape(4, 4)
+        w = np.asarray(p, np.float64).reshape(-1, 3) @ M[:3, :3] + M[3, :3]
+        points.append((w.min(0) + w.max(0)) / 2)
+    points = np.array(points)
+    target = (points.min(0) + points.max(0)) / 2
+    radius = np.linalg.norm(points - target, axis=1).max() + 4.0
+    eye = target + np.array([0.0, 0.45, 1.0]) * (radius / np.tan(fov_y / 2) / np.linalg.norm([0.45, 1.0]))
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(fwd, (0, 1, 0)); right /= np.linalg.norm(right)
+    up = np.cross(right, fwd)
+    view = np.eye(4)
+    view[0, :3], view[1, :3], view[2, :3] = right, up, -fwd
+    view[:3, 3] = -view[:3, :3] @ eye
+    t, near, far = 1.0 / np.tan(fov_y / 2), 0.1, 500.0
+    proj = np.zeros((4, 4))
+    proj[0, 0], proj[1, 1], proj[2, 2], proj[2, 3], proj[3, 2] = t * height / width, t, far / (near - far), far * near / (near - far), -1
+    mats = A.default_render_materials(4)   # 0 ground, 1 mirror, 2 platforms, 3 player
+    mats["baseColor"][0], mats["roughness"][0] = (0.55, 0.6, 0.5), 0.9
+    mats["baseColor"][1], mats["metallic"][1], mats["roughness"][1] = (0.9, 0.9, 0.95), 1.0, 0.0
+    mats["baseColor"][2], mats["roughness"][2] = (0.8, 0.45, 0.2), 0.6
+    mats["baseColor"][3], mats["roughness"][3] = (0.3, 0.5, 0.9), 0.5
+    engine.render_materials(mats)
+    engine.render_static_materials([0, 1] + [2] * (engine.scene_info().staticInstances - 2))
+    engine.render_crowd_materials([3])
+    light = np.zeros(1, A.render_light_dtype)   # RayTracingRenderer.swift:163-168's default light, from SUN's side
+    light["direction"], light["intensity"], light["color"], light["enabled"], light["maxDistance"] = -SUN, 2.6, (1.0, 0.95, 0.85), 1.0, 200.0
+    engine.render_lights(light)
+    sh = np.zeros((9, 3), np.float32)           # makeHemisphereSH's two terms (RayTracingRenderer.swift:190-198)
+    sh[0], sh[1] = np.array([0.5, 0.525, 0.6]) / 0.282095, np.array([0.2, 0.275, 0.4]) / 0.488603
+    frame = engine.render_frame_record(np.linalg.inv(proj @ view), eye.astype(np.float32), width, height, 1, ambient_intensity=0.25, env_sh=sh)
+    rgba, aov = engine.render_frame(frame, aov=True)
+    img = np.rint(np.clip(rgba[..., :3], 0.0, 1.0) * 255.0).astype(np.uint8)
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (width, height))
+        f.write(img.tobytes())
+    return aov
 
 
 def ascii_depth(mask, dist, shadow=None):
@@ -215,6 +265,7 @@ if __name__ == "__main__":
     ap.add_argument("--oracle", action="store_true", help="run the CPU checker (tests/oracle_binding.py) instead of the GPU library")
     ap.add_argument("--render", action="store_true", help="shoot primary rays and shadow rays at the whole scene (ground, mirror, platforms, player) after the last step and "
                     "print the depth image with shadowed pixels marked; with --oracle: primary rays at the characters only")
+    ap.add_argument("--image", metavar="PATH", help="with --render (GPU library): also write the shaded frame of the scene (ground, mirror, platforms, shadowed player; a wider camera of its own) as a binary PPM")
     args = ap.parse_args()
     if args.oracle:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -231,6 +282,12 @@ if __name__ == "__main__":
         print("primary rays: %d of %d hit the scene (%d the player, %d static instances), %d shadowed, distances %.3f .. %.3f" % (
             mask.sum(), mask.size, (ids < A.SCENE_STATIC_BASE).sum(), (ids >= A.SCENE_STATIC_BASE).sum(), shadow.sum(), dist[mask].min(), dist[mask].max()))
         print(ascii_depth(mask, dist, shadow))
+        if args.image:
+            aov = shaded_image(eng, args.image)
+            ids = aov["instance"]
+            print("shaded frame %s: %d x %d, %d queries; pixels: %d ground, %d mirror (%d through the mirror path), %d platforms, %d player, %d with the sun shadowed" % (
+                args.image, aov.shape[1], aov.shape[0], aov["queries"].sum(), (ids == A.SCENE_STATIC_BASE).sum(), (ids == A.SCENE_STATIC_BASE + 1).sum(),
+                (aov["flags"] & 1).sum(), (ids >= A.SCENE_STATIC_BASE + 2).sum(), (ids == 0).sum(), (aov["shadow"] < 1).sum()))
     elif args.render:
         mask, dist, hits = render_probe(eng)
         print("primary rays: %d of %d hit the player, distances %.3f .. %.3f" % (mask.sum(), mask.size, dist[mask].min(), dist[mask].max()))

@@ -391,6 +391,60 @@ SCENE_PROTOTYPES = {
     "sge_scene_occluded_device": (C.c_int, [VP, VP, i32, VP]),
 }
 
+
+# include/sge_amd_render.h: the shaded frame (raytraceKernel's layers, lights and bounces) over the ray scene.
+class RenderMaterial(C.Structure):
+    _fields_ = [("baseColor", f32 * 3), ("metallic", f32), ("emissive", f32 * 3), ("occlusionStrength", f32), ("roughness", f32),
+                ("alpha", f32), ("transmission", f32), ("ior", f32)]
+
+
+class RenderLight(C.Structure):
+    _fields_ = [("direction", f32 * 3), ("intensity", f32), ("color", f32 * 3), ("enabled", f32), ("maxDistance", f32), ("pad", f32 * 3)]
+
+
+class RenderFrame(C.Structure):
+    _fields_ = [("invViewProj", f32 * 16), ("cameraPosition", f32 * 3), ("ambientIntensity", f32), ("width", i32), ("height", i32),
+                ("dirLightCount", i32), ("flags", i32), ("envSH", (f32 * 3) * 9)]
+
+
+class RenderAov(C.Structure):
+    _fields_ = [("layers", i32), ("instance", i32), ("primitive", i32), ("distance", f32), ("shadow", f32), ("alpha", f32),
+                ("queries", i32), ("flags", i32)]
+
+
+assert (C.sizeof(RenderMaterial), C.sizeof(RenderLight), C.sizeof(RenderFrame), C.sizeof(RenderAov)) == (48, 48, 204, 32)
+render_material_dtype = np.dtype([("baseColor", "<f4", 3), ("metallic", "<f4"), ("emissive", "<f4", 3), ("occlusionStrength", "<f4"),
+                                  ("roughness", "<f4"), ("alpha", "<f4"), ("transmission", "<f4"), ("ior", "<f4")])
+render_light_dtype = np.dtype([("direction", "<f4", 3), ("intensity", "<f4"), ("color", "<f4", 3), ("enabled", "<f4"),
+                               ("maxDistance", "<f4"), ("pad", "<f4", 3)])
+render_frame_dtype = np.dtype([("invViewProj", "<f4", 16), ("cameraPosition", "<f4", 3), ("ambientIntensity", "<f4"), ("width", "<i4"),
+                               ("height", "<i4"), ("dirLightCount", "<i4"), ("flags", "<i4"), ("envSH", "<f4", (9, 3))])
+render_aov_dtype = np.dtype([("layers", "<i4"), ("instance", "<i4"), ("primitive", "<i4"), ("distance", "<f4"), ("shadow", "<f4"),
+                             ("alpha", "<f4"), ("queries", "<i4"), ("flags", "<i4")])
+for _dt, _st in ((render_material_dtype, RenderMaterial), (render_light_dtype, RenderLight), (render_frame_dtype, RenderFrame),
+                 (render_aov_dtype, RenderAov)):
+    assert _dt.itemsize == C.sizeof(_st), (_dt, _st)
+SGE_MAX_RENDER_MATERIALS = 256
+SGE_MAX_DIR_LIGHTS = 8
+SGE_MAX_RENDER_PIXELS = 1 << 26
+
+
+def default_render_materials(count=1):
+    """Material.swift:37-44: base (1,1,1), metallic 0, roughness 0.5, emissive 0, occlusion 1, alpha 1, transmission 0, ior 1.5."""
+    m = np.zeros(count, render_material_dtype)
+    m["baseColor"], m["occlusionStrength"], m["roughness"], m["alpha"], m["ior"] = 1.0, 1.0, 0.5, 1.0, 1.5
+    return m
+
+
+RENDER_PROTOTYPES = {
+    "sge_render_materials_set": (C.c_int, [VP, i32, VP]),
+    "sge_render_static_materials": (C.c_int, [VP, i32, VP]),
+    "sge_render_crowd_materials": (C.c_int, [VP, i32, VP]),
+    "sge_render_lights_set": (C.c_int, [VP, i32, VP]),
+    "sge_render_frame_batch": (C.c_int, [VP, VP, VP, VP]),
+    "sge_render_frame_device": (C.c_int, [VP, VP, VP, VP]),
+}
+
 LIB_NAME = "libsge_amd.so"
 
 
@@ -424,7 +478,7 @@ def load_library(path=None):
         raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = bind(C.CDLL(path))
-    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES):
+    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES, RENDER_PROTOTYPES):
         for name, (res, args) in table.items():  # (raises AttributeError if one is missing)
             fn = getattr(lib, name)
             fn.restype = res

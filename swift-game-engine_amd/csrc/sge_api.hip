@@ -172,6 +172,16 @@ struct sge_context {
     // sge_scene_instances_update: the caller's matrices go through pinned memory, so that its array is free on return
     struct SceneStage { void* host = nullptr; size_t bytes = 0; hipEvent_t copied = nullptr; bool inFlight = false; } sceneStage[2];
     int sceneStageSlot = 0;
+    // the shaded frame (include/sge_amd_render.h): the material table as uploaded (clamped on the device copy), who names which
+    // material, the lights as the kernel reads them, the launch record of the frame in flight, the batch form's outputs
+    std::vector<sge_render_material> hostMaterials{sge_render_material{{1, 1, 1}, 0, {0, 0, 0}, 1, 0.5f, 1, 0, 1.5f}};
+    std::vector<int32_t> hostStaticMaterial, hostCrowdMaterial; // valid while their length is the instance / character count
+    int renderLights = 0;
+    const void* renderStaticListSeen = nullptr; // dSceneMeshOf when the static assignment was made: sge_scene_instances_set replaces it
+    // the launch record of a frame goes through pinned memory (as sceneStage): sge_render_frame_device does not wait for the stream
+    struct RenderStage { void* host = nullptr; hipEvent_t copied = nullptr; bool inFlight = false; } renderStage[2];
+    int renderStageSlot = 0;
+    DevBuf dRenderMaterials, dRenderStaticMaterial, dRenderCrowdMaterial, dRenderLights, dRenderArgs, dRenderRGBA, dRenderAOV;
     // stats / profiling
     DevBuf dStats, dWaveProf, dOrderHist, dSepAgents, dSepCounts, dSepFlow;
     int separationIterations = 2; float separationMargin = 0.2f, separationHeightMargin = 0.1f; // AgentSeparationSystem.init :2146-2152
@@ -745,6 +755,78 @@ int checkSceneMatrices(const char* who, const float* m, int count) {
     return SGE_OK;
 }
 
+
+// ---- the shaded frame (include/sge_amd_render.h) ----
+// the device copy of the material table: every entry as sample_material clamps it (RayTracing.metalinc:143-150)
+int uploadRenderMaterials(sge_context* c) {
+    std::vector<sge_render_material> dev(SGE_MAX_RENDER_MATERIALS, c->hostMaterials[0]);
+    for (size_t i = 0; i < c->hostMaterials.size(); ++i) {
+        sge_render_material m = c->hostMaterials[i];
+        m.alpha = fminf(fmaxf(m.alpha, 0.0f), 1.0f);
+        m.metallic = fminf(fmaxf(m.metallic, 0.0f), 1.0f);
+        m.roughness = fminf(fmaxf(m.roughness, 0.05f), 1.0f);
+        m.occlusionStrength = fminf(fmaxf(m.occlusionStrength, 0.0f), 1.0f);
+        m.transmission = fminf(fmaxf(m.transmission, 0.0f), 1.0f);
+        m.ior = fmaxf(m.ior, 1.0f);
+        dev[i] = m;
+    }
+    int rc = upload(c->dRenderMaterials, dev.data(), dev.size() * sizeof(sge_render_material), c->stream);
+    if (rc != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    return SGE_OK;
+}
+// An assignment lives until the list it assigns is replaced: sge_scene_instances_set (another count, or another device list) and
+// sge_characters_resize (another count) are observed here, by every sge_render_* entry before it does anything else, and the
+// assignment is dropped for good: a later list of the old length starts from material 0 again.
+void dropStaleRenderAssignments(sge_context* c) {
+    if (!c->hostStaticMaterial.empty() && ((int)c->hostStaticMaterial.size() != c->sceneStatics || c->renderStaticListSeen != c->dSceneMeshOf.p)) c->hostStaticMaterial.clear();
+    if (!c->hostCrowdMaterial.empty() && (int)c->hostCrowdMaterial.size() != c->crowd.count) c->hostCrowdMaterial.clear();
+}
+bool staticMaterialsValid(const sge_context* c) { return !c->hostStaticMaterial.empty(); }
+bool crowdMaterialsValid(const sge_context* c) { return !c->hostCrowdMaterial.empty(); }
+int checkRenderFrame(const sge_context* c, const sge_render_frame* f) {
+    const float* p = reinterpret_cast<const float*>(f);
+    for (int k = 0; k < 20; ++k)
+        if (!std::isfinite(p[k])) { set_error("sge_render_frame: the frame has a non-finite entry"); return SGE_ERR_INVALID; }
+    for (int k = 0; k < 27; ++k)
+        if (!std::isfinite(f->envSH[k / 3][k % 3])) { set_error("sge_render_frame: the frame has a non-finite entry"); return SGE_ERR_INVALID; }
+    if (f->width < 1 || f->height < 1 || (long long)f->width * f->height > SGE_MAX_RENDER_PIXELS) { set_error("sge_render_frame: image size out of range (SGE_MAX_RENDER_PIXELS)"); return SGE_ERR_INVALID; }
+    if (f->flags != 0) { set_error("sge_render_frame: flags must be 0"); return SGE_ERR_INVALID; }
+    if (f->dirLightCount < 0 || f->dirLightCount > c->renderLights) { set_error("sge_render_frame: dirLightCount above the uploaded light count"); return SGE_ERR_INVALID; }
+    return SGE_OK;
+}
+// everything of a frame's launch on the context's stream; the caller has ordered the stream behind the skin stage
+int enqueueRenderFrame(sge_context* c, const sge_render_frame* f, float* d_rgba, sge_render_aov* d_aov) {
+    int rc;
+    if (!c->dRenderMaterials.p && (rc = uploadRenderMaterials(c)) != SGE_OK) return rc;
+    if ((rc = c->dRenderLights.alloc(SGE_MAX_DIR_LIGHTS * sizeof(DevRenderLight))) != SGE_OK) return rc;
+    if ((rc = c->dRenderArgs.alloc(2 * sizeof(RenderArgs))) != SGE_OK) return rc;
+    // two pinned slots taken in turn, each with its own device copy: the host waits only for the copy of the frame before last
+    const int slot = c->renderStageSlot;
+    sge_context::RenderStage& st = c->renderStage[slot];
+    c->renderStageSlot ^= 1;
+    if (st.inFlight) { SGE_HIP(hipEventSynchronize(st.copied)); st.inFlight = false; }
+    if (!st.copied) SGE_HIP(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    if (!st.host) SGE_HIP(hipHostMalloc(&st.host, sizeof(RenderArgs), hipHostMallocDefault));
+    RenderArgs& A = *reinterpret_cast<RenderArgs*>(st.host);
+    A = RenderArgs{};
+    if ((rc = sceneTrace(c, A.S)) != SGE_OK) return rc;
+    A.R.frame = *f;
+    A.R.materials = c->dRenderMaterials.as<sge_render_material>();
+    A.R.staticMaterial = staticMaterialsValid(c) ? c->dRenderStaticMaterial.as<int>() : nullptr;
+    A.R.crowdMaterial = crowdMaterialsValid(c) ? c->dRenderCrowdMaterial.as<int>() : nullptr;
+    A.R.lights = c->dRenderLights.as<DevRenderLight>();
+    A.R.rgba = d_rgba;
+    A.R.aov = d_aov;
+    RenderArgs* d_args = c->dRenderArgs.as<RenderArgs>() + slot;
+    SGE_HIP(hipMemcpyAsync(d_args, st.host, sizeof(RenderArgs), hipMemcpyHostToDevice, c->stream));
+    SGE_HIP(hipEventRecord(st.copied, c->stream));
+    st.inFlight = true;
+    launch_render_frame(A, d_args, c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -858,6 +940,8 @@ void sge_context_destroy(sge_context* c) {
         for (DevBuf* b : {&sm.entryLink, &sm.wideFirst, &sm.slotIdx, &sm.slotTri, &sm.boxes, &sm.pos, &sm.nrm, &sm.tan, &sm.uvs, &sm.indices}) b->release();
     for (DevBuf* b : {&c->dSceneTable, &c->dSceneMeshOf, &c->dSceneMatrices, &c->dSceneBoxes, &c->dSceneOccluded}) b->release();
     for (auto& st : c->sceneStage) { if (st.host) (void)hipHostFree(st.host); if (st.copied) (void)hipEventDestroy(st.copied); }
+    for (auto& st : c->renderStage) { if (st.host) (void)hipHostFree(st.host); if (st.copied) (void)hipEventDestroy(st.copied); }
+    for (DevBuf* b : {&c->dRenderMaterials, &c->dRenderStaticMaterial, &c->dRenderCrowdMaterial, &c->dRenderLights, &c->dRenderArgs, &c->dRenderRGBA, &c->dRenderAOV}) b->release();
     for (DevBuf* b : {&c->dVariantTable, &c->dVariantOf, &c->dVariantSnap[0], &c->dVariantSnap[1], &c->dVertexOff, &c->dVariantLists, &c->dSkinPlan}) b->release();
     for (hipEvent_t e : {c->evVariantSnap, c->evPlanDone[0], c->evPlanDone[1], c->variantStage[0].copied, c->variantStage[1].copied}) if (e) (void)hipEventDestroy(e);
     for (auto& st : c->variantStage) if (st.host) (void)hipHostFree(st.host);
@@ -2633,6 +2717,101 @@ int sge_scene_occluded_device(sge_context* c, const void* d_rays, int32_t count,
     launch_scene_occlusion(S, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<int32_t*>(d_occluded), c->stream);
     SGE_HIP(hipGetLastError());
     return SGE_OK;
+}
+
+// ---- the shaded frame (include/sge_amd_render.h) ----
+int sge_render_materials_set(sge_context* c, int32_t count, const struct sge_render_material* materials) {
+    if (!c || !materials || count < 1 || count > SGE_MAX_RENDER_MATERIALS) { set_error("sge_render_materials_set: bad argument (1 .. SGE_MAX_RENDER_MATERIALS materials)"); return SGE_ERR_INVALID; }
+    dropStaleRenderAssignments(c);
+    const float* p = reinterpret_cast<const float*>(materials);
+    for (size_t k = 0; k < (size_t)count * 12; ++k)
+        if (!std::isfinite(p[k])) { set_error("sge_render_materials_set: a material has a non-finite field"); return SGE_ERR_INVALID; }
+    int used = 0;
+    if (staticMaterialsValid(c)) for (int32_t m : c->hostStaticMaterial) used = std::max(used, (int)m);
+    if (crowdMaterialsValid(c)) for (int32_t m : c->hostCrowdMaterial) used = std::max(used, (int)m);
+    if (used >= count) { set_error("sge_render_materials_set: the table would end below a material index still in use"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    const std::vector<sge_render_material> before = c->hostMaterials;
+    c->hostMaterials.assign(materials, materials + count);
+    const int rc = uploadRenderMaterials(c);
+    if (rc != SGE_OK) c->hostMaterials = before;
+    return rc;
+}
+
+static int setRenderMaterialIndices(sge_context* c, const char* who, int32_t count, int expected, const int32_t* idx, std::vector<int32_t>& host, DevBuf& dev) {
+    if (!c || count < 0 || (count > 0 && !idx)) { set_error(std::string(who) + ": bad argument"); return SGE_ERR_INVALID; }
+    dropStaleRenderAssignments(c);
+    if (count != expected) { set_error(std::string(who) + ": count differs from the number of instances it assigns"); return SGE_ERR_INVALID; }
+    for (int i = 0; i < count; ++i)
+        if (idx[i] < 0 || idx[i] >= (int)c->hostMaterials.size()) { set_error(std::string(who) + ": a material index outside the table"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    if (count > 0) {
+        int rc = upload(dev, idx, (size_t)count * sizeof(int32_t), c->stream);
+        if (rc != SGE_OK) return rc;
+        SGE_HIP(hipStreamSynchronize(c->stream));
+    }
+    host.assign(idx, idx + count);
+    if (&host == &c->hostStaticMaterial) c->renderStaticListSeen = c->dSceneMeshOf.p;
+    return SGE_OK;
+}
+int sge_render_static_materials(sge_context* c, int32_t count, const int32_t* material_of_instance) {
+    if (!c) { set_error("sge_render_static_materials: bad argument"); return SGE_ERR_INVALID; }
+    return setRenderMaterialIndices(c, "sge_render_static_materials", count, c->sceneStatics, material_of_instance, c->hostStaticMaterial, c->dRenderStaticMaterial);
+}
+int sge_render_crowd_materials(sge_context* c, int32_t count, const int32_t* material_of_character) {
+    if (!c) { set_error("sge_render_crowd_materials: bad argument"); return SGE_ERR_INVALID; }
+    return setRenderMaterialIndices(c, "sge_render_crowd_materials", count, c->crowd.count, material_of_character, c->hostCrowdMaterial, c->dRenderCrowdMaterial);
+}
+
+int sge_render_lights_set(sge_context* c, int32_t count, const struct sge_render_light* lights) {
+    if (!c || count < 0 || count > SGE_MAX_DIR_LIGHTS || (count > 0 && !lights)) { set_error("sge_render_lights_set: bad argument (0 .. SGE_MAX_DIR_LIGHTS lights)"); return SGE_ERR_INVALID; }
+    const float* p = reinterpret_cast<const float*>(lights);
+    for (size_t k = 0; k < (size_t)count * 12; ++k)
+        if (!std::isfinite(p[k])) { set_error("sge_render_lights_set: a light has a non-finite field"); return SGE_ERR_INVALID; }
+    DevRenderLight dev[SGE_MAX_DIR_LIGHTS] = {};
+    for (int i = 0; i < count; ++i) { // the header's pinned forms (this file is built without contraction)
+        const sge_render_light& l = lights[i];
+        const F3 d = -F3{l.direction[0], l.direction[1], l.direction[2]};
+        const F3 L = d / sqrtf(dot(d, d));
+        dev[i] = DevRenderLight{{L.x, L.y, L.z}, l.enabled, {l.color[0] * l.intensity, l.color[1] * l.intensity, l.color[2] * l.intensity},
+                                l.maxDistance > 0.0f ? l.maxDistance : 1e6f};
+    }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    int rc = upload(c->dRenderLights, dev, sizeof(dev), c->stream);
+    if (rc != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    c->renderLights = count;
+    return SGE_OK;
+}
+
+int sge_render_frame_batch(sge_context* c, const struct sge_render_frame* frame, float* rgba, struct sge_render_aov* aov) {
+    if (!c || !frame || !rgba) { set_error("sge_render_frame_batch: bad argument"); return SGE_ERR_INVALID; }
+    { int rcf = checkRenderFrame(c, frame); if (rcf != SGE_OK) return rcf; }
+    dropStaleRenderAssignments(c);
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    const size_t n = (size_t)frame->width * frame->height;
+    int rc;
+    if ((rc = c->dRenderRGBA.alloc(n * 16)) != SGE_OK) return rc;
+    if (aov && (rc = c->dRenderAOV.alloc(n * sizeof(sge_render_aov))) != SGE_OK) return rc;
+    if ((rc = enqueueRenderFrame(c, frame, c->dRenderRGBA.as<float>(), aov ? c->dRenderAOV.as<sge_render_aov>() : nullptr)) != SGE_OK) return rc;
+    // (into the caller's arrays only behind a launch that succeeded: on failure they are untouched)
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    SGE_HIP(hipMemcpy(rgba, c->dRenderRGBA.p, n * 16, hipMemcpyDeviceToHost));
+    if (aov) SGE_HIP(hipMemcpy(aov, c->dRenderAOV.p, n * sizeof(sge_render_aov), hipMemcpyDeviceToHost));
+    return SGE_OK;
+}
+
+int sge_render_frame_device(sge_context* c, const struct sge_render_frame* frame, void* d_rgba, void* d_aov) {
+    if (!c || !frame || !d_rgba) { set_error("sge_render_frame_device: bad argument"); return SGE_ERR_INVALID; }
+    { int rcf = checkRenderFrame(c, frame); if (rcf != SGE_OK) return rcf; }
+    dropStaleRenderAssignments(c);
+    (void)hipSetDevice(c->device);
+    { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
+    return enqueueRenderFrame(c, frame, reinterpret_cast<float*>(d_rgba), reinterpret_cast<sge_render_aov*>(d_aov));
 }
 
 int sge_blas_profile_read(sge_context* c, double* ms, int64_t* launches, int reset) {

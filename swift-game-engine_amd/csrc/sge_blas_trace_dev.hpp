@@ -171,16 +171,22 @@ __device__ __forceinline__ void blasTraverseClosest(int* stack, int lane, const 
     }
 }
 
+// The face-forwarded geometric normal of a hit triangle with object-space vertices v0, v1, v2 (RayTracing.metalinc:258-268): the
+// geomNormal of the hit record, and the N the shaded frame (sge_render.hip) shades with.
+__device__ __forceinline__ F3 blasFaceNormal(const Aff& M, F3 v0, F3 v1, F3 v2, F3 wd) {
+    const F3 w0 = affMulPoint(M, v0), w1 = affMulPoint(M, v1), w2 = affMulPoint(M, v2);
+    F3 N = normalize(cross(w1 - w0, w2 - w0));
+    if (dot(N, wd) > 0.0f) N = -N;
+    return N;
+}
+
 // What raytraceKernel derives at a hit (RayTracing.metalinc:258-300) from one instance's streams: P and NB with STRIDE floats per
 // vertex, TB with four, uvs with two (or null), `ix` the three indices of the hit triangle. Fills everything but H.instance.
 template <int STRIDE>
 __device__ __forceinline__ void blasHitRecord(const Aff& M, const float* P, const float* NB, const float* TB, const float* uvs, const uint32_t* ix,
                                               F3 wd, const BlasBest& B, sge_blas_hit& H) {
     const uint32_t i0 = ix[0], i1 = ix[1], i2 = ix[2];
-    // RayTracing.metalinc:258-268
-    const F3 w0 = affMulPoint(M, loadP<STRIDE>(P, i0)), w1 = affMulPoint(M, loadP<STRIDE>(P, i1)), w2 = affMulPoint(M, loadP<STRIDE>(P, i2));
-    F3 N = normalize(cross(w1 - w0, w2 - w0));
-    if (dot(N, wd) > 0.0f) N = -N;
+    const F3 N = blasFaceNormal(M, loadP<STRIDE>(P, i0), loadP<STRIDE>(P, i1), loadP<STRIDE>(P, i2), wd);
     // :283-300
     const float bx = B.u, by = B.v, bw = 1.0f - bx - by;
     const F3 n0 = loadP<STRIDE>(NB, i0), n1 = loadP<STRIDE>(NB, i1), n2 = loadP<STRIDE>(NB, i2);

@@ -8,6 +8,7 @@
 #include "../../include/sge_amd_variants.h"
 #include "../../include/sge_amd_variant_blas.h"
 #include "../../include/sge_amd_ray_scene.h"
+#include "../../include/sge_amd_render.h"
 #include "sge_math.hpp"
 
 namespace sge {
@@ -27,6 +28,8 @@ static_assert(sizeof(sge_tick_desc) == 32, "layout");
 static_assert(sizeof(sge_skin_plan_info) == 64, "layout");
 static_assert(sizeof(struct sge_blas_variant_layout) == 48, "layout");
 static_assert(sizeof(struct sge_scene_info) == 16, "layout");
+static_assert(sizeof(struct sge_render_material) == 48 && sizeof(struct sge_render_light) == 48, "layout");
+static_assert(sizeof(struct sge_render_frame) == 204 && sizeof(struct sge_render_aov) == 32, "layout");
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
@@ -481,5 +484,23 @@ struct SceneTrace {
 void launch_scene_instance_boxes(const SceneTrace& S, int firstGroup, int groups, hipStream_t s);
 void launch_scene_trace(const SceneTrace& S, const sge_blas_ray* d_rays, int n, sge_blas_hit* d_hits, hipStream_t s);
 void launch_scene_occlusion(const SceneTrace& S, const sge_blas_ray* d_rays, int n, int32_t* d_occluded, hipStream_t s);
+
+// ---- the shaded frame (include/sge_amd_render.h, sge_render.hip) ---- //
+// A light as the kernel reads it, prepared once by sge_render_lights_set in the header's pinned float32 forms:
+// L = normalize(-direction), Li = color * intensity, maxDist = maxDistance > 0 ? maxDistance : 1e6 (RayTracing.metalinc:325-328, :374).
+struct DevRenderLight { float L[3]; float enabled; float Li[3]; float maxDist; };
+struct RenderLaunch {
+    sge_render_frame frame;
+    const sge_render_material* materials; // device table, every entry clamped as sample_material clamps it (:143-150)
+    const int* staticMaterial;            // [statics] or null: every static instance uses material 0
+    const int* crowdMaterial;             // [chars] or null
+    const DevRenderLight* lights;         // device [SGE_MAX_DIR_LIGHTS]
+    float* rgba;                          // [height][width][4]
+    sge_render_aov* aov;                  // [height][width] or null
+};
+// One wavefront per pixel. The kernel reads both records from device memory: `d_args` holds a copy of `host` (S as
+// launch_scene_trace takes it), made on `s` before the launch.
+struct RenderArgs { SceneTrace S; RenderLaunch R; };
+void launch_render_frame(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
 
 } // namespace sge

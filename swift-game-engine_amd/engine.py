@@ -619,6 +619,52 @@ class CharacterEngine:
         """Rays and int32 words already in device memory; asynchronous on the context's stream."""
         self._call("scene_occluded_device", C.c_void_p(d_rays), int(count), C.c_void_p(d_occluded))
 
+    # -- the shaded frame: raytraceKernel over the ray scene (include/sge_amd_render.h; product only) -- #
+    def render_materials(self, materials):
+        """Replaces the material table: abi.render_material_dtype records (see abi.default_render_materials)."""
+        m = np.ascontiguousarray(materials, abi.render_material_dtype).reshape(-1)
+        self._call("render_materials_set", m.shape[0], ptr(m))
+
+    def render_static_materials(self, material_of_instance):
+        idx = np.ascontiguousarray(material_of_instance, np.int32).reshape(-1)
+        self._call("render_static_materials", idx.shape[0], ptr(idx))
+
+    def render_crowd_materials(self, material_of_character):
+        idx = np.ascontiguousarray(material_of_character, np.int32).reshape(-1)
+        self._call("render_crowd_materials", idx.shape[0], ptr(idx))
+
+    def render_lights(self, lights):
+        """abi.render_light_dtype records, at most abi.SGE_MAX_DIR_LIGHTS."""
+        l = np.ascontiguousarray(lights, abi.render_light_dtype).reshape(-1)
+        self._call("render_lights_set", l.shape[0], ptr(l))
+
+    @staticmethod
+    def render_frame_record(inv_view_proj, camera_position, width, height, dir_light_count, ambient_intensity=0.25, env_sh=None):
+        """One abi.render_frame_dtype record; inv_view_proj is a row-major numpy 4x4 (stored column-major, as the ABI takes it)."""
+        f = np.zeros(1, abi.render_frame_dtype)
+        f["invViewProj"][0] = np.asarray(inv_view_proj, np.float32).reshape(4, 4).T.reshape(16)
+        f["cameraPosition"][0] = camera_position
+        f["ambientIntensity"], f["width"], f["height"], f["dirLightCount"] = ambient_intensity, width, height, dir_light_count
+        if env_sh is not None:
+            f["envSH"][0] = np.asarray(env_sh, np.float32).reshape(9, 3)
+        return f
+
+    def render_frame(self, frame, aov=False):
+        """raytraceKernel -> float32 rgba [height][width][4] (and abi.render_aov_dtype [height][width] with aov=True)."""
+        f = np.ascontiguousarray(frame, abi.render_frame_dtype).reshape(1)
+        h, w = int(f["height"][0]), int(f["width"][0])
+        n = max(h, 0) * max(w, 0) if 0 < h * w <= abi.SGE_MAX_RENDER_PIXELS else 1
+        rgba = np.zeros((n, 4), np.float32)
+        a = np.zeros(n, abi.render_aov_dtype) if aov else None
+        self._call("render_frame_batch", ptr(f), ptr(rgba), ptr(a))
+        rgba = rgba.reshape(h, w, 4)
+        return (rgba, a.reshape(h, w)) if aov else rgba
+
+    def render_frame_device(self, frame, d_rgba, d_aov=0):
+        """The image (and the AOV records) into device memory; asynchronous on the context's stream."""
+        f = np.ascontiguousarray(frame, abi.render_frame_dtype).reshape(1)
+        self._call("render_frame_device", ptr(f), C.c_void_p(d_rgba), C.c_void_p(d_aov) if d_aov else None)
+
     def blas_profile(self, reset=True):
         ms, n = C.c_double(0), C.c_int64(0)
         self._call("blas_profile_read", C.byref(ms), C.byref(n), int(reset))

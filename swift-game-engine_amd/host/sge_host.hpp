@@ -27,6 +27,7 @@
 #include <unordered_set>
 #include <vector>
 #include "../../include/sge_amd.h"
+#include "../../include/sge_amd_render.h"
 
 namespace sge {
 
@@ -264,6 +265,111 @@ public:
         sge_blas_info i{};
         check(sge_blas_info_get(world_->context(), &i), "sge_blas_info_get");
         return i;
+    }
+
+private:
+    World* world_;
+};
+
+// RayTracingRenderer.encode (RayTracingRenderer.swift:55-109) over the ray scene of the context: the frame uniforms, the light
+// buffer and the dispatch of raytraceKernel (include/sge_amd_render.h). The scene itself — static meshes and instances
+// (sge_scene_*), the crowd's structure (RTAccelerationBuilder above), materials (setMaterials / setStaticMaterials /
+// setCrowdMaterials: RTInstanceInfo's factors) — is set up by the caller, as rtScene's buffers are built before :63-64 return.
+struct DirectionalLight {   // Components.swift DirectionalLight as updateLightBuffers reads it (RayTracingRenderer.swift:170-177)
+    float direction[3] = {-0.2f, -1.0f, -0.4f};
+    float intensity = 2.6f;
+    float color[3] = {1.0f, 0.95f, 0.85f};
+    bool enabled = true;
+    float maxDistance = 200.0f;
+};
+
+class RayTracingRenderer {
+public:
+    explicit RayTracingRenderer(World& w) : world_(&w) {}
+    void setMaterials(const std::vector<sge_render_material>& m) { check(sge_render_materials_set(world_->context(), (int32_t)m.size(), m.data()), "sge_render_materials_set"); }
+    void setStaticMaterials(const std::vector<int32_t>& m) { check(sge_render_static_materials(world_->context(), (int32_t)m.size(), m.data()), "sge_render_static_materials"); }
+    void setCrowdMaterials(const std::vector<int32_t>& m) { check(sge_render_crowd_materials(world_->context(), (int32_t)m.size(), m.data()), "sge_render_crowd_materials"); }
+
+    // :66-97: invViewProj = simd_inverse(projection * viewMatrix) (both column-major), imageSize at least 1 x 1, ambientIntensity
+    // 0.25, the two hemisphere terms of makeHemisphereSH (:190-198); dirLightCount = lights.count
+    static sge_render_frame makeFrame(int width, int height, const float cameraPosition[3], const float projection[16], const float viewMatrix[16], int lightCount) {
+        sge_render_frame f{};
+        float vp[16];
+        for (int c = 0; c < 4; ++c)
+            for (int r = 0; r < 4; ++r) {
+                float a = 0;
+                for (int k = 0; k < 4; ++k) a += projection[k * 4 + r] * viewMatrix[c * 4 + k];
+                vp[c * 4 + r] = a;
+            }
+        if (!inverse4(vp, f.invViewProj)) throw Error("RayTracingRenderer: projection * view is singular");
+        for (int k = 0; k < 3; ++k) f.cameraPosition[k] = cameraPosition[k];
+        f.ambientIntensity = 0.25f;
+        f.width = std::max(width, 1);
+        f.height = std::max(height, 1);
+        f.dirLightCount = lightCount;
+        const float sky[3] = {0.7f, 0.8f, 1.0f}, ground[3] = {0.3f, 0.25f, 0.2f};
+        for (int k = 0; k < 3; ++k) {
+            f.envSH[0][k] = ((sky[k] + ground[k]) * 0.5f) / 0.282095f;
+            f.envSH[1][k] = ((sky[k] - ground[k]) * 0.5f) / 0.488603f;
+        }
+        return f;
+    }
+
+    // updateLightBuffers (:153-180). An empty list uploads the default light of :163-168, and the frame still says
+    // dirLightCount = 0 (:85): the kernel then shades with ambient and emission only. That is the reference's behaviour, kept.
+    void updateLightBuffers(const std::vector<DirectionalLight>& lights) {
+        std::vector<sge_render_light> l(std::max<size_t>(lights.size(), 1));
+        const DirectionalLight fallback{};
+        for (size_t i = 0; i < l.size(); ++i) {
+            const DirectionalLight& s = lights.empty() ? fallback : lights[i];
+            sge_render_light d{};
+            for (int k = 0; k < 3; ++k) { d.direction[k] = s.direction[k]; d.color[k] = s.color[k]; }
+            d.intensity = s.intensity;
+            d.enabled = s.enabled ? 1.0f : 0.0f;
+            d.maxDistance = s.maxDistance;
+            l[i] = d;
+        }
+        check(sge_render_lights_set(world_->context(), (int32_t)l.size(), l.data()), "sge_render_lights_set");
+    }
+
+    // encode (:55-109) into host memory: rgba[height][width][4]; aov[height][width] or null. Synchronises.
+    void encode(int width, int height, const std::vector<DirectionalLight>& lights, const float cameraPosition[3], const float projection[16],
+                const float viewMatrix[16], float* rgba, sge_render_aov* aov = nullptr) {
+        const sge_render_frame f = makeFrame(width, height, cameraPosition, projection, viewMatrix, (int)lights.size());
+        updateLightBuffers(lights);
+        check(sge_render_frame_batch(world_->context(), &f, rgba, aov), "sge_render_frame_batch");
+    }
+    // the same into device memory, enqueued on the context's stream behind the tick's skin and refit launches
+    void encodeDevice(int width, int height, const std::vector<DirectionalLight>& lights, const float cameraPosition[3], const float projection[16],
+                      const float viewMatrix[16], void* d_rgba, void* d_aov = nullptr) {
+        const sge_render_frame f = makeFrame(width, height, cameraPosition, projection, viewMatrix, (int)lights.size());
+        updateLightBuffers(lights);
+        check(sge_render_frame_device(world_->context(), &f, d_rgba, d_aov), "sge_render_frame_device");
+    }
+
+    // the inverse of a column-major 4x4 by cofactors; false when the determinant is 0
+    static bool inverse4(const float m[16], float out[16]) {
+        float inv[16];
+        inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
+        inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
+        inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
+        inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
+        inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
+        inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
+        inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
+        inv[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
+        inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
+        inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
+        inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
+        inv[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
+        inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
+        inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
+        inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
+        inv[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
+        const float det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12];
+        if (det == 0.0f) return false;
+        for (int k = 0; k < 16; ++k) out[k] = inv[k] / det;
+        return true;
     }
 
 private:

@@ -1,0 +1,156 @@
+"""Diagnostic: ms per shaded frame (include/sge_amd_render.h) on one MI355X, image and AOV records resident on the device.
+
+The scene of tools/scene_ray_bench.py: the settled 10,000-character crowd, the 17-Cheese render mesh as one static instance and
+1,000 instances of a small box, with a mix of opaque, mirror and glass materials on the characters and the boxes, two lights (light
+0 shadowed). One process; sge_render_frame_device at 1280 x 720 from a camera above the crowd's edge, timed with HIP events on the
+context's stream after a warm-up frame; queries per second from the sum of the AOV records' `queries`. For context only, in the
+same run and alternating with the frames: sge_scene_intersect_device on the frame's primary rays alone.
+usage: render_bench.py [--chars N] [--boxes K] [--width W] [--height H] [--frames F] [--out FILE]"""
+import importlib, os, sys
+import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sge = importlib.import_module("swift-game-engine_amd")
+abi = sge.abi
+import torch
+
+arg = lambda k, d, cast=int: cast(sys.argv[sys.argv.index(k) + 1]) if k in sys.argv else d
+n, boxes, W, H, frames = arg("--chars", 10000), arg("--boxes", 1000), arg("--width", 1280), arg("--height", 720), arg("--frames", 5)
+out_path = arg("--out", None, str)
+lines = []
+
+
+def say(text):
+    print(text, flush=True)
+    lines.append(text)
+
+
+def flat_normals(pos, idx):
+    tri = np.asarray(idx, np.int64).reshape(-1, 3)
+    fn = np.cross(pos[tri[:, 1]] - pos[tri[:, 0]], pos[tri[:, 2]] - pos[tri[:, 0]]).astype(np.float64)
+    nrm = np.zeros(pos.shape, np.float64)
+    for k in range(3):
+        np.add.at(nrm, tri[:, k], fn)
+    length = np.linalg.norm(nrm, axis=1, keepdims=True)
+    return np.where(length > 0, nrm / np.maximum(length, 1e-30), (0.0, 1.0, 0.0)).astype(np.float32)
+
+
+def upload_mesh(eng, mesh, pos, idx):
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+    return eng.scene_mesh_upload(mesh, pos, flat_normals(pos, idx), np.tile(np.array([1, 0, 0, 1], np.float32), (len(pos), 1)), idx)
+
+
+eng = sge.CharacterEngine(0)
+ybot = sge.assets.YBotAssets()
+sge.crowd.upload_character_assets(eng, ybot)
+terrain = sge.crowd.upload_terrain(eng)
+sge.crowd.spawn_crowd(eng, ybot, n, terrain, mode="ccd")
+eng.blas_build(eng.mesh["indices"])
+for _ in range(130):
+    eng.tick(stages=abi.STAGE_ALL | abi.STAGE_BLAS_REFIT)
+b = eng.download(what=("bodies",))["bodies"]
+P = b["position"].astype(np.float32)
+mats = np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+mats[:, 3, :3] = P                                            # column-major: translation in the last column
+eng.blas_instances(mats.reshape(n, 16))
+
+# statics as in scene_ray_bench.py
+cheese = sge.crowd._load_static_parts("cheese")[0]
+cpos = np.asarray(cheese["positions"], np.float32).reshape(-1, 3)
+info = upload_mesh(eng, 0, cpos, cheese["indices"])
+bp = np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], np.float32)
+bi = np.array([0, 1, 3, 0, 3, 2, 4, 6, 7, 4, 7, 5, 0, 4, 5, 0, 5, 1, 2, 3, 7, 2, 7, 6, 0, 2, 6, 0, 6, 4, 1, 5, 7, 1, 7, 3], np.uint32)
+upload_mesh(eng, 1, bp, bi)
+rng = np.random.default_rng(1)
+lo, hi = P.min(0), P.max(0)
+scale = np.float32((hi - lo)[[0, 2]].max() / 6 / max(np.ptp(cpos, axis=0).max(), 1e-6))
+S = np.tile(np.eye(4, dtype=np.float32), (1 + boxes, 1, 1))
+S[0, :3, :3] *= scale
+S[0, 3, :3] = (lo + hi) / 2 - scale * (cpos.min(0) + cpos.max(0)) / 2 * (1, 0, 1) - (0, scale * cpos[:, 1].min(), 0)
+S[1:, 3, :3] = np.stack([rng.uniform(lo[0], hi[0], boxes), rng.uniform(lo[1], hi[1], boxes) + 1.0, rng.uniform(lo[2], hi[2], boxes)], 1)
+eng.scene_instances(np.array([0] + [1] * boxes, np.int32), S.reshape(-1, 16))
+
+# materials: 0 opaque rough, 1 mirror, 2 glass; a third of the characters and of the boxes each
+m = abi.default_render_materials(3)
+m["baseColor"][0], m["roughness"][0] = (0.7, 0.6, 0.5), 0.7
+m["baseColor"][1], m["metallic"][1], m["roughness"][1] = (0.9, 0.9, 0.95), 1.0, 0.0
+m["baseColor"][2], m["transmission"][2], m["alpha"][2], m["ior"][2] = (0.7, 0.9, 0.8), 0.8, 0.4, 1.5
+eng.render_materials(m)
+eng.render_static_materials(np.concatenate([[0], np.arange(boxes) % 3]).astype(np.int32))
+eng.render_crowd_materials((np.arange(n) % 3).astype(np.int32))
+light = np.zeros(2, abi.render_light_dtype)
+light["direction"], light["intensity"], light["color"], light["enabled"] = [(-0.2, -1.0, -0.4), (0.5, -0.6, 0.4)], [2.6, 0.5], [(1.0, 0.95, 0.85), (0.6, 0.7, 1.0)], 1.0
+light["maxDistance"] = [0.0, 0.0]
+eng.render_lights(light)
+
+# the camera: above the middle of the crowd's front edge, looking at its centre
+ext = float((hi - lo)[[0, 2]].max())
+centre = ((lo + hi) / 2).astype(np.float64)
+eye = centre + (0.0, 0.18 * ext, 0.62 * ext)
+fwd = (centre - eye) / np.linalg.norm(centre - eye)
+right = np.cross(fwd, (0, 1, 0)); right /= np.linalg.norm(right)
+up = np.cross(right, fwd)
+view = np.eye(4)
+view[0, :3], view[1, :3], view[2, :3] = right, up, -fwd
+view[:3, 3] = -view[:3, :3] @ eye
+t, near, far = 1.0 / np.tan(np.radians(50.0) / 2), 0.1, 2000.0
+proj = np.zeros((4, 4))
+proj[0, 0], proj[1, 1], proj[2, 2], proj[2, 3], proj[3, 2] = t * H / W, t, far / (near - far), far * near / (near - far), -1
+sh = np.zeros((9, 3), np.float32)
+sh[0], sh[1] = np.array([0.5, 0.525, 0.6]) / 0.282095, np.array([0.2, 0.275, 0.4]) / 0.488603
+inv = np.linalg.inv(proj @ view)
+frame = eng.render_frame_record(inv, eye.astype(np.float32), W, H, 2, ambient_intensity=0.25, env_sh=sh)
+
+# the frame's primary rays, for the context figure
+gy, gx = np.divmod(np.arange(W * H), W)
+ndc = np.stack([(gx + 0.5) / W * 2 - 1, (1 - (gy + 0.5) / H) * 2 - 1, np.ones(W * H), np.ones(W * H)], 1)
+world = ndc @ inv.T
+d = world[:, :3] / world[:, 3:4] - eye
+d /= np.linalg.norm(d, axis=1, keepdims=True)
+r = np.zeros(W * H, abi.blas_ray_dtype)
+r["origin"], r["direction"], r["minDistance"], r["maxDistance"], r["instance"] = eye.astype(np.float32), d.astype(np.float32), 0.001, 1e6, -1
+d_r = torch.from_numpy(r.view(np.uint8).copy()).to("cuda:0")
+d_h = torch.zeros(W * H * abi.blas_hit_dtype.itemsize, dtype=torch.uint8, device="cuda:0")
+d_rgba = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
+d_aov = torch.zeros(W * H * abi.render_aov_dtype.itemsize, dtype=torch.uint8, device="cuda:0")
+torch.cuda.synchronize()
+stream = torch.cuda.ExternalStream(eng.stream_handle(), device="cuda:0")
+
+forms = {"render_frame_device": lambda: eng.render_frame_device(frame, d_rgba.data_ptr(), d_aov.data_ptr()),
+         "scene_intersect_device": lambda: eng.scene_intersect_device(d_r.data_ptr(), W * H, d_h.data_ptr())}
+for k in forms:
+    forms[k]()
+eng.synchronize()
+ms = {k: [] for k in forms}
+for _ in range(frames):
+    for k in forms:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        forms[k]()
+        e1.record(stream)
+        e1.synchronize()
+        ms[k].append(e0.elapsed_time(e1))
+eng.synchronize()
+aov = d_aov.cpu().numpy().view(abi.render_aov_dtype)
+hits = d_h.cpu().numpy().view(abi.blas_hit_dtype)
+rgba = d_rgba.cpu().numpy().reshape(H, W, 4)
+queries = int(aov["queries"].sum())
+
+say("render_bench: %d x %d, %d characters + 17-Cheese (%d triangles) + %d boxes, opaque / mirror / glass materials, 2 lights" % (W, H, n, info.triangleCount, boxes))
+v = np.array(ms["render_frame_device"])
+say("  sge_render_frame_device     %s ms  median %.3f  min %.3f  max %.3f" % (" ".join("%.3f" % x for x in v), np.median(v), v.min(), v.max()))
+say("    = %.2f Mpixels/s, %.1f M queries/s (%d queries per frame, %.2f per pixel, at most %d in one pixel)" % (
+    W * H / np.median(v) / 1e3, queries / np.median(v) / 1e3, queries, queries / (W * H), aov["queries"].max()))
+say("    pixels: %.0f %% hit; layers 0/1/2/3: %s; %.1f %% through the mirror path, %.1f %% through the refraction path, %.1f %% with light 0 shadowed" % (
+    100 * (aov["instance"] >= 0).mean(), " ".join("%.1f %%" % (100 * (aov["layers"] == k).mean()) for k in range(4)),
+    100 * ((aov["flags"] & 1) != 0).mean(), 100 * ((aov["flags"] & 2) != 0).mean(), 100 * (aov["shadow"] < 1).mean()))
+p = np.array(ms["scene_intersect_device"])
+say("  context: sge_scene_intersect_device on the frame's primary rays alone  %s ms  median %.3f = %.1f M rays/s (%.0f %% hit)" % (
+    " ".join("%.3f" % x for x in p), np.median(p), W * H / np.median(p) / 1e3, 100 * hits["hit"].mean()))
+say("  the frame's queries per second / the primary rays' rays per second = %.2f" % ((queries / np.median(v)) / (W * H / np.median(p))))
+assert np.isfinite(rgba).all() and (rgba[..., 3] == 1).all()
+if out_path:
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+eng.close()
