@@ -20,11 +20,13 @@
  * sge_blas_intersect_batch.
  *
  * The crowd is optional. A context with no skinned mesh, no characters or no sge_blas_build traces the static half alone, and a
- * ray that names a character misses. A context with mesh variants (sge_amd_variants.h) also traces the statics only and
- * sge_scene_info_get reports crowdReady = 0: tracing a crowd of mixed variants through these entry points is not implemented
- * (sge_blas_intersect_* of sge_amd_variant_blas.h does trace it). sge_blas_intersect_* is unchanged and sees characters only.
- * Where sge_blas_intersect_* returns SGE_ERR_STATE, these entry points do not fail: they leave the crowd out, and crowdReady = 0
- * is the only sign of it. crowdReady is 1 exactly when all of these hold: no mesh variant is uploaded; sge_skinned_mesh_upload
+ * ray that names a character misses. A context with mesh variants (sge_amd_variants.h) is traced through these entry points once
+ * every variant has its structure: sge_amd_variant_scene.h states that contract and the per-character semantics. While a variant
+ * lacks its structure such a context traces the statics only and sge_scene_info_get reports crowdReady = 0.
+ * sge_blas_intersect_* is unchanged and sees characters only.
+ * Where sge_blas_intersect_* returns SGE_ERR_STATE, these entry points do not fail: they leave the crowd out and report
+ * crowdReady = 0 (sge_amd_variant_scene.h adds the reason). For a crowd that shares one mesh crowdReady is 1 exactly when all of
+ * these hold: sge_skinned_mesh_upload
  * and sge_blas_build have been called, the latter after the newest mesh upload; sge_characters_resize gave a count > 0; the
  * per-character boxes and instance matrices exist for that count (sge_blas_build or sge_characters_resize, whichever came
  * last, allocates them) and so do the skinned output streams. A renderer checks it once after setting up the crowd.

@@ -45,8 +45,8 @@
  * list of the same length starts from material 0 again. (Two sge_scene_instances_set calls with no sge_render_* call between them
  * are one replacement.)
  *
- * The crowd is optional, exactly as in sge_amd_ray_scene.h: with crowdReady == 0 (mesh variants included) the frame shows the
- * statics only.
+ * The crowd is optional, exactly as in sge_amd_ray_scene.h: with crowdReady == 0 the frame shows the statics only. A crowd with
+ * mesh variants is in the frame once every variant has its structure (sge_amd_variant_scene.h).
  *
  * Ordering. sge_render_frame_batch synchronises. sge_render_frame_device is enqueued on the context's stream with exactly the
  * contract of sge_scene_intersect_device: behind the skin and refit launches of the newest sge_tick under every

@@ -445,6 +445,20 @@ RENDER_PROTOTYPES = {
     "sge_render_frame_device": (C.c_int, [VP, VP, VP, VP]),
 }
 
+
+# include/sge_amd_variant_scene.h: a crowd with mesh variants in the ray scene and the shaded frame.
+class SceneCrowdStatus(C.Structure):
+    _fields_ = [("crowdReady", i32), ("ragged", i32), ("reason", i32), ("variant", i32)]
+
+
+assert C.sizeof(SceneCrowdStatus) == 16
+(SCENE_CROWD_OK, SCENE_CROWD_NO_MESH, SCENE_CROWD_NO_STRUCTURE, SCENE_CROWD_NO_CHARACTERS, SCENE_CROWD_VARIANT_NOT_BUILT,
+ SCENE_CROWD_NO_BUFFERS) = range(6)
+
+VARIANT_SCENE_PROTOTYPES = {
+    "sge_scene_crowd_status_get": (C.c_int, [VP, P(SceneCrowdStatus)]),
+}
+
 LIB_NAME = "libsge_amd.so"
 
 
@@ -478,7 +492,7 @@ def load_library(path=None):
         raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = bind(C.CDLL(path))
-    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES, RENDER_PROTOTYPES):
+    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES, RENDER_PROTOTYPES, VARIANT_SCENE_PROTOTYPES):
         for name, (res, args) in table.items():  # (raises AttributeError if one is missing)
             fn = getattr(lib, name)
             fn.restype = res

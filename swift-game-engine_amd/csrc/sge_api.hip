@@ -696,11 +696,30 @@ int crowdTrace(sge_context* c, bool anyInstance, BlasTrace& T) {
 }
 
 // ---- the ray scene (include/sge_amd_ray_scene.h) ----
-// "The crowd is optional": one shared mesh with a structure, characters, and the buffers sge_blas_build / sge_characters_resize keep
-bool sceneCrowdReady(const sge_context* c) {
-    return c->extraVariants == 0 && c->mesh.vertexCount > 0 && c->blas.entryCount > 0 && c->crowd.count > 0 &&
-           c->blasBoundsChars == c->crowd.count && c->dBlasBounds.p && c->dBlasInstances.p && c->dOutPos.p && c->dOutNrm.p && c->dOutTan.p;
+// "The crowd is optional": a mesh with a structure, characters, and the buffers sge_blas_build / sge_characters_resize keep — for
+// a crowd that shares one mesh the uniform box table, for a crowd with mesh variants (include/sge_amd_variant_scene.h) the READY of
+// sge_amd_variant_blas.h and the ragged box table, records and offsets. The first condition that fails is the reason reported;
+// VARIANT_NOT_BUILT can only apply to a context with variants, NO_BUFFERS means the uniform box table for a crowd that shares one
+// mesh and the ragged table, records, offsets and device table for a crowd with variants.
+sge_scene_crowd_status sceneCrowdStatus(const sge_context* c) {
+    sge_scene_crowd_status st{0, 0, SGE_SCENE_CROWD_OK, -1};
+    const bool streams = c->dBlasInstances.p && c->blasBoundsChars == c->crowd.count && c->dOutPos.p && c->dOutNrm.p && c->dOutTan.p;
+    if (c->mesh.vertexCount <= 0) st.reason = SGE_SCENE_CROWD_NO_MESH;
+    else if (c->blas.entryCount <= 0) st.reason = SGE_SCENE_CROWD_NO_STRUCTURE;
+    else if (c->crowd.count <= 0) st.reason = SGE_SCENE_CROWD_NO_CHARACTERS;
+    else if (c->extraVariants > 0) {
+        for (int v = 1; v <= c->extraVariants; ++v)
+            if (!c->vblas[v].built) { st.reason = SGE_SCENE_CROWD_VARIANT_NOT_BUILT; st.variant = v; break; }
+        if (st.reason == SGE_SCENE_CROWD_OK) {
+            if (streams && variantBlasReady(c) && c->varBoundsChars == c->crowd.count && c->varRowStride > 0 && c->dVarBounds.p && c->dCharVariant.p &&
+                c->dVertexOff.p && c->dVarBlasTable.p) st.ragged = 1;
+            else st.reason = SGE_SCENE_CROWD_NO_BUFFERS;
+        }
+    } else if (!(streams && c->dBlasBounds.p)) st.reason = SGE_SCENE_CROWD_NO_BUFFERS;
+    st.crowdReady = st.reason == SGE_SCENE_CROWD_OK ? 1 : 0;
+    return st;
 }
+bool sceneCrowdReady(const sge_context* c) { return sceneCrowdStatus(c).crowdReady != 0; }
 // the static half of a launch; S.crowd / S.T are filled by sceneTrace
 SceneTrace sceneStatics(sge_context* c) {
     SceneTrace S{};
@@ -711,11 +730,45 @@ SceneTrace sceneStatics(sge_context* c) {
     S.statics = c->sceneStatics;
     return S;
 }
-// + the crowd half with its instance level refreshed (whole-scene rays are always allowed)
-int sceneTrace(sge_context* c, SceneTrace& S) {
+// + the crowd half with its instance level refreshed (whole-scene rays are always allowed). *ragged = true: the crowd has mesh
+// variants; S.T is then the ragged record's T and G what the ragged kernels read beside it.
+int sceneTrace(sge_context* c, SceneTrace& S, SceneRagged& G, bool* ragged) {
     S = sceneStatics(c);
-    S.crowd = sceneCrowdReady(c) ? 1 : 0;
-    return S.crowd ? crowdTrace(c, true, S.T) : SGE_OK;
+    G = SceneRagged{};
+    const sge_scene_crowd_status st = sceneCrowdStatus(c);
+    S.crowd = st.crowdReady;
+    *ragged = st.ragged != 0;
+    if (!S.crowd) return SGE_OK;
+    if (!st.ragged) return crowdTrace(c, true, S.T);
+    RaggedTrace R = variantTrace(c);
+    const int rc = buildInstanceLevel(c, R.T, &R);
+    if (rc != SGE_OK) return rc;
+    S.T = R.T;
+    G = SceneRagged{R.table, R.charVariant, R.off, R.rowStride};
+    return SGE_OK;
+}
+// the two queries over what sceneTrace filled, on the context's stream
+int enqueueSceneTrace(sge_context* c, const sge_blas_ray* d_rays, int count, sge_blas_hit* d_hits) {
+    SceneTrace S;
+    SceneRagged G;
+    bool ragged;
+    const int rc = sceneTrace(c, S, G, &ragged);
+    if (rc != SGE_OK) return rc;
+    if (ragged) launch_scene_trace_ragged(S, G, d_rays, count, d_hits, c->stream);
+    else launch_scene_trace(S, d_rays, count, d_hits, c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+int enqueueSceneOcclusion(sge_context* c, const sge_blas_ray* d_rays, int count, int32_t* d_occluded) {
+    SceneTrace S;
+    SceneRagged G;
+    bool ragged;
+    const int rc = sceneTrace(c, S, G, &ragged);
+    if (rc != SGE_OK) return rc;
+    if (ragged) launch_scene_occlusion_ragged(S, G, d_rays, count, d_occluded, c->stream);
+    else launch_scene_occlusion(S, d_rays, count, d_occluded, c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
 }
 // the entry boxes of a static mesh by the structure's definition (include/sge_amd.h): a leaf entry's box is the min / max of the
 // vertices of its triangles, an inner entry's the union of its wide node's entries, the last row the union of the root's entries
@@ -810,7 +863,8 @@ int enqueueRenderFrame(sge_context* c, const sge_render_frame* f, float* d_rgba,
     if (!st.host) SGE_HIP(hipHostMalloc(&st.host, sizeof(RenderArgs), hipHostMallocDefault));
     RenderArgs& A = *reinterpret_cast<RenderArgs*>(st.host);
     A = RenderArgs{};
-    if ((rc = sceneTrace(c, A.S)) != SGE_OK) return rc;
+    bool ragged;
+    if ((rc = sceneTrace(c, A.S, A.G, &ragged)) != SGE_OK) return rc;
     A.R.frame = *f;
     A.R.materials = c->dRenderMaterials.as<sge_render_material>();
     A.R.staticMaterial = staticMaterialsValid(c) ? c->dRenderStaticMaterial.as<int>() : nullptr;
@@ -822,7 +876,8 @@ int enqueueRenderFrame(sge_context* c, const sge_render_frame* f, float* d_rgba,
     SGE_HIP(hipMemcpyAsync(d_args, st.host, sizeof(RenderArgs), hipMemcpyHostToDevice, c->stream));
     SGE_HIP(hipEventRecord(st.copied, c->stream));
     st.inFlight = true;
-    launch_render_frame(A, d_args, c->stream);
+    if (ragged) launch_render_frame_ragged(A, d_args, c->stream);
+    else launch_render_frame(A, d_args, c->stream);
     SGE_HIP(hipGetLastError());
     return SGE_OK;
 }
@@ -2659,6 +2714,12 @@ int sge_scene_info_get(sge_context* c, struct sge_scene_info* info) {
     return SGE_OK;
 }
 
+int sge_scene_crowd_status_get(sge_context* c, struct sge_scene_crowd_status* out) {
+    if (!c || !out) { set_error("sge_scene_crowd_status_get: bad argument"); return SGE_ERR_INVALID; }
+    *out = sceneCrowdStatus(c);
+    return SGE_OK;
+}
+
 int sge_scene_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t count, sge_blas_hit* hits) {
     if (!c || count < 0 || (count > 0 && (!rays || !hits))) { set_error("sge_scene_intersect_batch: bad argument"); return SGE_ERR_INVALID; }
     if (count == 0) return SGE_OK;
@@ -2667,10 +2728,7 @@ int sge_scene_intersect_batch(sge_context* c, const sge_blas_ray* rays, int32_t 
     int rc;
     if ((rc = upload(c->dBlasRays, rays, (size_t)count * sizeof(sge_blas_ray), c->stream)) != SGE_OK) return rc;
     if ((rc = c->dBlasHits.alloc((size_t)count * sizeof(sge_blas_hit))) != SGE_OK) return rc;
-    SceneTrace S;
-    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
-    launch_scene_trace(S, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>(), c->stream);
-    SGE_HIP(hipGetLastError());
+    if ((rc = enqueueSceneTrace(c, c->dBlasRays.as<sge_blas_ray>(), count, c->dBlasHits.as<sge_blas_hit>())) != SGE_OK) return rc;
     SGE_HIP(hipMemcpyAsync(hits, c->dBlasHits.p, (size_t)count * sizeof(sge_blas_hit), hipMemcpyDeviceToHost, c->stream));
     SGE_HIP(hipStreamSynchronize(c->stream));
     return SGE_OK;
@@ -2681,12 +2739,7 @@ int sge_scene_intersect_device(sge_context* c, const void* d_rays, int32_t count
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
     { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
-    int rc;
-    SceneTrace S;
-    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
-    launch_scene_trace(S, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits), c->stream);
-    SGE_HIP(hipGetLastError());
-    return SGE_OK;
+    return enqueueSceneTrace(c, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<sge_blas_hit*>(d_hits));
 }
 
 int sge_scene_occluded_batch(sge_context* c, const sge_blas_ray* rays, int32_t count, int32_t* occluded) {
@@ -2697,10 +2750,7 @@ int sge_scene_occluded_batch(sge_context* c, const sge_blas_ray* rays, int32_t c
     int rc;
     if ((rc = upload(c->dBlasRays, rays, (size_t)count * sizeof(sge_blas_ray), c->stream)) != SGE_OK) return rc;
     if ((rc = c->dSceneOccluded.alloc((size_t)count * sizeof(int32_t))) != SGE_OK) return rc;
-    SceneTrace S;
-    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
-    launch_scene_occlusion(S, c->dBlasRays.as<sge_blas_ray>(), count, c->dSceneOccluded.as<int32_t>(), c->stream);
-    SGE_HIP(hipGetLastError());
+    if ((rc = enqueueSceneOcclusion(c, c->dBlasRays.as<sge_blas_ray>(), count, c->dSceneOccluded.as<int32_t>())) != SGE_OK) return rc;
     SGE_HIP(hipMemcpyAsync(occluded, c->dSceneOccluded.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     SGE_HIP(hipStreamSynchronize(c->stream));
     return SGE_OK;
@@ -2711,12 +2761,7 @@ int sge_scene_occluded_device(sge_context* c, const void* d_rays, int32_t count,
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
     { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
-    int rc;
-    SceneTrace S;
-    if ((rc = sceneTrace(c, S)) != SGE_OK) return rc;
-    launch_scene_occlusion(S, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<int32_t*>(d_occluded), c->stream);
-    SGE_HIP(hipGetLastError());
-    return SGE_OK;
+    return enqueueSceneOcclusion(c, reinterpret_cast<const sge_blas_ray*>(d_rays), count, reinterpret_cast<int32_t*>(d_occluded));
 }
 
 // ---- the shaded frame (include/sge_amd_render.h) ----

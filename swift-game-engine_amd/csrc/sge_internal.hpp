@@ -9,6 +9,7 @@
 #include "../../include/sge_amd_variant_blas.h"
 #include "../../include/sge_amd_ray_scene.h"
 #include "../../include/sge_amd_render.h"
+#include "../../include/sge_amd_variant_scene.h"
 #include "sge_math.hpp"
 
 namespace sge {
@@ -484,6 +485,16 @@ struct SceneTrace {
 void launch_scene_instance_boxes(const SceneTrace& S, int firstGroup, int groups, hipStream_t s);
 void launch_scene_trace(const SceneTrace& S, const sge_blas_ray* d_rays, int n, sge_blas_hit* d_hits, hipStream_t s);
 void launch_scene_occlusion(const SceneTrace& S, const sge_blas_ray* d_rays, int n, int32_t* d_occluded, hipStream_t s);
+// The crowd half of a context with mesh variants (include/sge_amd_variant_scene.h, sge_scene_variants.hip): what RaggedTrace holds
+// beside its BlasTrace. S.T is then that record's T: blas / indices / uvs unused, bounds = [chars][rowStride][6].
+struct SceneRagged {
+    const DevVariantBlas* table;        // device
+    const uint8_t* charVariant;         // [chars] device: 0xFF = no boxes (never entered)
+    const long long* off;               // [chars + 1] device
+    int rowStride;
+};
+void launch_scene_trace_ragged(const SceneTrace& S, const SceneRagged& G, const sge_blas_ray* d_rays, int n, sge_blas_hit* d_hits, hipStream_t s);
+void launch_scene_occlusion_ragged(const SceneTrace& S, const SceneRagged& G, const sge_blas_ray* d_rays, int n, int32_t* d_occluded, hipStream_t s);
 
 // ---- the shaded frame (include/sge_amd_render.h, sge_render.hip) ---- //
 // A light as the kernel reads it, prepared once by sge_render_lights_set in the header's pinned float32 forms:
@@ -500,7 +511,9 @@ struct RenderLaunch {
 };
 // One wavefront per pixel. The kernel reads both records from device memory: `d_args` holds a copy of `host` (S as
 // launch_scene_trace takes it), made on `s` before the launch.
-struct RenderArgs { SceneTrace S; RenderLaunch R; };
+// (G: behind the two records the uniform kernel reads; filled and read only when the crowd has mesh variants)
+struct RenderArgs { SceneTrace S; RenderLaunch R; SceneRagged G; };
 void launch_render_frame(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
+void launch_render_frame_ragged(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
 
 } // namespace sge

@@ -585,6 +585,13 @@ class CharacterEngine:
         self._call("scene_info_get", C.byref(info))
         return info
 
+    def scene_crowd_status(self):
+        """What the scene and frame entry points do with the crowd (include/sge_amd_variant_scene.h) -> abi.SceneCrowdStatus:
+        crowdReady, ragged (traced through the per-variant table), reason (abi.SCENE_CROWD_*), variant."""
+        st = abi.SceneCrowdStatus()
+        self._call("scene_crowd_status_get", C.byref(st))
+        return st
+
     @staticmethod
     def _scene_rays(origins, directions, instances, min_distance, max_distance):
         o = np.asarray(origins, np.float32).reshape(-1, 3)

@@ -28,6 +28,7 @@
 #include <vector>
 #include "../../include/sge_amd.h"
 #include "../../include/sge_amd_render.h"
+#include "../../include/sge_amd_variant_scene.h"
 
 namespace sge {
 
@@ -289,6 +290,12 @@ public:
     void setMaterials(const std::vector<sge_render_material>& m) { check(sge_render_materials_set(world_->context(), (int32_t)m.size(), m.data()), "sge_render_materials_set"); }
     void setStaticMaterials(const std::vector<int32_t>& m) { check(sge_render_static_materials(world_->context(), (int32_t)m.size(), m.data()), "sge_render_static_materials"); }
     void setCrowdMaterials(const std::vector<int32_t>& m) { check(sge_render_crowd_materials(world_->context(), (int32_t)m.size(), m.data()), "sge_render_crowd_materials"); }
+    // whether the frame shows the crowd, through which table, and what is missing when it does not (include/sge_amd_variant_scene.h)
+    sge_scene_crowd_status crowdStatus() const {
+        sge_scene_crowd_status st{};
+        check(sge_scene_crowd_status_get(world_->context(), &st), "sge_scene_crowd_status_get");
+        return st;
+    }
 
     // :66-97: invViewProj = simd_inverse(projection * viewMatrix) (both column-major), imageSize at least 1 x 1, ambientIntensity
     // 0.25, the two hemisphere terms of makeHemisphereSH (:190-198); dirLightCount = lights.count

@@ -5,7 +5,10 @@ The scene of tools/scene_ray_bench.py: the settled 10,000-character crowd, the 1
 0 shadowed). One process; sge_render_frame_device at 1280 x 720 from a camera above the crowd's edge, timed with HIP events on the
 context's stream after a warm-up frame; queries per second from the sum of the AOV records' `queries`. For context only, in the
 same run and alternating with the frames: sge_scene_intersect_device on the frame's primary rays alone.
-usage: render_bench.py [--chars N] [--boxes K] [--width W] [--height H] [--frames F] [--out FILE]"""
+With --variants, behind those lines and in the same process: the same frame, statics, materials and lights for the crowd with three
+mesh variants chosen by sge_lod_select from the camera (tools/variant_crowd.py) — first the control, whose variants all hold the full
+mesh (the ragged frame kernel over the uniform crowd's geometry), then full / half / quarter vertex count.
+usage: render_bench.py [--chars N] [--boxes K] [--width W] [--height H] [--frames F] [--variants] [--out FILE]"""
 import importlib, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -114,43 +117,70 @@ d_h = torch.zeros(W * H * abi.blas_hit_dtype.itemsize, dtype=torch.uint8, device
 d_rgba = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
 d_aov = torch.zeros(W * H * abi.render_aov_dtype.itemsize, dtype=torch.uint8, device="cuda:0")
 torch.cuda.synchronize()
-stream = torch.cuda.ExternalStream(eng.stream_handle(), device="cuda:0")
 
-forms = {"render_frame_device": lambda: eng.render_frame_device(frame, d_rgba.data_ptr(), d_aov.data_ptr()),
-         "scene_intersect_device": lambda: eng.scene_intersect_device(d_r.data_ptr(), W * H, d_h.data_ptr())}
-for k in forms:
-    forms[k]()
-eng.synchronize()
-ms = {k: [] for k in forms}
-for _ in range(frames):
+def measure(eng, label, uniform=None):
+    """frames alternating with the primary-ray launch; prints the lines -> median ms of the frame"""
+    stream = torch.cuda.ExternalStream(eng.stream_handle(), device="cuda:0")
+    forms = {"render_frame_device": lambda: eng.render_frame_device(frame, d_rgba.data_ptr(), d_aov.data_ptr()),
+             "scene_intersect_device": lambda: eng.scene_intersect_device(d_r.data_ptr(), W * H, d_h.data_ptr())}
     for k in forms:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
         forms[k]()
-        e1.record(stream)
-        e1.synchronize()
-        ms[k].append(e0.elapsed_time(e1))
-eng.synchronize()
-aov = d_aov.cpu().numpy().view(abi.render_aov_dtype)
-hits = d_h.cpu().numpy().view(abi.blas_hit_dtype)
-rgba = d_rgba.cpu().numpy().reshape(H, W, 4)
-queries = int(aov["queries"].sum())
+    eng.synchronize()
+    ms = {k: [] for k in forms}
+    for _ in range(frames):
+        for k in forms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            forms[k]()
+            e1.record(stream)
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    eng.synchronize()
+    aov = d_aov.cpu().numpy().view(abi.render_aov_dtype)
+    hits = d_h.cpu().numpy().view(abi.blas_hit_dtype)
+    rgba = d_rgba.cpu().numpy().reshape(H, W, 4)
+    queries = int(aov["queries"].sum())
 
-say("render_bench: %d x %d, %d characters + 17-Cheese (%d triangles) + %d boxes, opaque / mirror / glass materials, 2 lights" % (W, H, n, info.triangleCount, boxes))
-v = np.array(ms["render_frame_device"])
-say("  sge_render_frame_device     %s ms  median %.3f  min %.3f  max %.3f" % (" ".join("%.3f" % x for x in v), np.median(v), v.min(), v.max()))
-say("    = %.2f Mpixels/s, %.1f M queries/s (%d queries per frame, %.2f per pixel, at most %d in one pixel)" % (
-    W * H / np.median(v) / 1e3, queries / np.median(v) / 1e3, queries, queries / (W * H), aov["queries"].max()))
-say("    pixels: %.0f %% hit; layers 0/1/2/3: %s; %.1f %% through the mirror path, %.1f %% through the refraction path, %.1f %% with light 0 shadowed" % (
-    100 * (aov["instance"] >= 0).mean(), " ".join("%.1f %%" % (100 * (aov["layers"] == k).mean()) for k in range(4)),
-    100 * ((aov["flags"] & 1) != 0).mean(), 100 * ((aov["flags"] & 2) != 0).mean(), 100 * (aov["shadow"] < 1).mean()))
-p = np.array(ms["scene_intersect_device"])
-say("  context: sge_scene_intersect_device on the frame's primary rays alone  %s ms  median %.3f = %.1f M rays/s (%.0f %% hit)" % (
-    " ".join("%.3f" % x for x in p), np.median(p), W * H / np.median(p) / 1e3, 100 * hits["hit"].mean()))
-say("  the frame's queries per second / the primary rays' rays per second = %.2f" % ((queries / np.median(v)) / (W * H / np.median(p))))
-assert np.isfinite(rgba).all() and (rgba[..., 3] == 1).all()
+    say(label)
+    v = np.array(ms["render_frame_device"])
+    say("  sge_render_frame_device     %s ms  median %.3f  min %.3f  max %.3f" % (" ".join("%.3f" % x for x in v), np.median(v), v.min(), v.max()))
+    say("    = %.2f Mpixels/s, %.1f M queries/s (%d queries per frame, %.2f per pixel, at most %d in one pixel)" % (
+        W * H / np.median(v) / 1e3, queries / np.median(v) / 1e3, queries, queries / (W * H), aov["queries"].max()))
+    say("    pixels: %.0f %% hit; layers 0/1/2/3: %s; %.1f %% through the mirror path, %.1f %% through the refraction path, %.1f %% with light 0 shadowed" % (
+        100 * (aov["instance"] >= 0).mean(), " ".join("%.1f %%" % (100 * (aov["layers"] == k).mean()) for k in range(4)),
+        100 * ((aov["flags"] & 1) != 0).mean(), 100 * ((aov["flags"] & 2) != 0).mean(), 100 * (aov["shadow"] < 1).mean()))
+    p = np.array(ms["scene_intersect_device"])
+    say("  context: sge_scene_intersect_device on the frame's primary rays alone  %s ms  median %.3f = %.1f M rays/s (%.0f %% hit)" % (
+        " ".join("%.3f" % x for x in p), np.median(p), W * H / np.median(p) / 1e3, 100 * hits["hit"].mean()))
+    say("  the frame's queries per second / the primary rays' rays per second = %.2f" % ((queries / np.median(v)) / (W * H / np.median(p))))
+    assert np.isfinite(rgba).all() and (rgba[..., 3] == 1).all()
+    if uniform is not None:
+        say("  frame median / the uniform line's median = %.3f" % (np.median(v) / uniform))
+    return float(np.median(v))
+
+
+def dress(eng):
+    """statics, materials and lights of the frame"""
+    upload_mesh(eng, 0, cpos, cheese["indices"])
+    upload_mesh(eng, 1, bp, bi)
+    eng.scene_instances(np.array([0] + [1] * boxes, np.int32), S.reshape(-1, 16))
+    eng.render_materials(m)
+    eng.render_static_materials(np.concatenate([[0], np.arange(boxes) % 3]).astype(np.int32))
+    eng.render_crowd_materials((np.arange(n) % 3).astype(np.int32))
+    eng.render_lights(light)
+
+
+uniform_ms = measure(eng, "render_bench: %d x %d, %d characters + 17-Cheese (%d triangles) + %d boxes, opaque / mirror / glass materials, 2 lights" % (W, H, n, info.triangleCount, boxes))
+eng.close()
+if "--variants" in sys.argv:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from variant_crowd import settled_crowd
+    for mode, what in (("control", "three variants that all hold the full mesh"), ("lod", "full / half / quarter vertex count")):
+        eng, P2, per, verts = settled_crowd(sge, n, mode, lambda a, b: eye)
+        dress(eng)
+        measure(eng, "(%s) mesh variants, %s: vertices per variant %s, characters per variant %s (sge_lod_select from the camera)" % (mode, what, verts, per), uniform_ms)
+        eng.close()
 if out_path:
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         f.write("\n".join(lines) + "\n")
-eng.close()

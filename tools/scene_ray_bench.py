@@ -7,7 +7,11 @@ events on the context's stream after a warm-up launch of both.
       reference; the scene form should sit within the spread of the reference's own five runs
   (b) whole-scene closest hit, rays/s
   (c) occlusion on the same rays; it does a subset of (b)'s work and must not be slower
-usage: scene_ray_bench.py [--chars N] [--rays M] [--boxes K] [--out FILE]"""
+With --variants, behind those lines and in the same process: (b) and (c) again, on the same rays and statics, for the crowd with three
+mesh variants chosen by sge_lod_select (tools/variant_crowd.py) — first the control, whose variants all hold the full mesh (the
+ragged kernels over the uniform crowd's geometry: the price of the per-character table walk alone, read against the uniform lines
+above), then full / half / quarter vertex count.
+usage: scene_ray_bench.py [--chars N] [--rays M] [--boxes K] [--variants] [--out FILE]"""
 import importlib, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -86,9 +90,15 @@ d_o = torch.zeros(m, dtype=torch.int32, device="cuda:0")
 torch.cuda.synchronize()
 stream = torch.cuda.ExternalStream(eng.stream_handle(), device="cuda:0")
 
-forms = {"blas_intersect_device": lambda: eng.blas_intersect_device(d_r.data_ptr(), m, d_h.data_ptr()),
-         "scene_intersect_device": lambda: eng.scene_intersect_device(d_r.data_ptr(), m, d_h.data_ptr()),
-         "scene_occluded_device": lambda: eng.scene_occluded_device(d_r.data_ptr(), m, d_o.data_ptr())}
+
+
+def forms_of(e):
+    return {"blas_intersect_device": lambda: e.blas_intersect_device(d_r.data_ptr(), m, d_h.data_ptr()),
+            "scene_intersect_device": lambda: e.scene_intersect_device(d_r.data_ptr(), m, d_h.data_ptr()),
+            "scene_occluded_device": lambda: e.scene_occluded_device(d_r.data_ptr(), m, d_o.data_ptr())}
+
+
+forms = forms_of(eng)
 
 
 def alternate(a, b, rounds=5):
@@ -132,8 +142,34 @@ say("  %.0f %% of the rays hit (%.0f %% of the hits are static instances); occlu
     100 * h["hit"].mean(), 100 * (h["instance"][h["hit"] == 1] >= abi.SCENE_STATIC_BASE).mean(), (occ == h["hit"]).sum(), m))
 say("  occlusion median / closest-hit median = %.3f (%s)" % (np.median(occms) / np.median(hitms),
                                                                "not slower" if np.median(occms) <= np.median(hitms) else "SLOWER: a defect"))
+eng.close()
+
+if "--variants" in sys.argv:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from variant_crowd import settled_crowd
+    uniform = {"scene_intersect_device": np.median(hitms), "scene_occluded_device": np.median(occms)}
+    ext = float((hi - lo)[[0, 2]].max())
+    for mode, what in (("control", "three variants that all hold the full mesh"), ("lod", "full / half / quarter vertex count")):
+        # the eye of tools/render_bench.py's camera: above the middle of the crowd's front edge
+        eng, P2, per, verts = settled_crowd(sge, n, mode, lambda a, b: (a + b) / 2 + (0.0, 0.18 * ext, 0.62 * ext))
+        upload_mesh(eng, 0, cpos, cheese["indices"])
+        upload_mesh(eng, 1, bp, bi)
+        eng.scene_instances(mesh_of, S.reshape(-1, 16))
+        stream = torch.cuda.ExternalStream(eng.stream_handle(), device="cuda:0")
+        forms = forms_of(eng)
+        say("(%s) mesh variants, %s: vertices per variant %s, characters per variant %s (sge_lod_select); max |position - uniform run's| = %.3g" % (
+            mode, what, verts, per, float(np.abs(P2 - P).max())))
+        ms = alternate("scene_intersect_device", "scene_occluded_device")
+        for k in ("scene_intersect_device", "scene_occluded_device"):
+            v = report(k, ms[k])
+            say("    median / the uniform line's median = %.3f" % (np.median(v) / uniform[k]))
+        eng.synchronize()
+        h = d_h.cpu().numpy().view(abi.blas_hit_dtype)
+        occ = d_o.cpu().numpy()
+        say("  %.0f %% of the rays hit (%.0f %% of the hits are static instances); occluded == hit for %d of %d rays" % (
+            100 * h["hit"].mean(), 100 * (h["instance"][h["hit"] == 1] >= abi.SCENE_STATIC_BASE).mean(), (occ == h["hit"]).sum(), m))
+        eng.close()
 if out_path:
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         f.write("\n".join(lines) + "\n")
-eng.close()
