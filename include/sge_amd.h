@@ -714,6 +714,18 @@ int sge_debug_wave_profile(sge_context* ctx, uint64_t* out, int32_t waves);
 /* Diagnostics: the scheduling lists of the last move launch: lists[0 .. counts[0]) = the grouped launch's characters ordered by last
    step's cost, lists[count .. count + counts[1]) = the multi-wave launch's characters (lists holds 2 * count entries). */
 int sge_debug_move_lists(sge_context* ctx, int32_t* lists, int32_t* counts);
+/* Diagnostics: the move stage's scheduling state as it stands in device memory once every stream of the context has drained, for the
+   range [first, first + count) (count 0: the whole crowd) of the NEWEST tick with SGE_STAGE_MOVE (any other range: SGE_ERR_STATE).
+   Whose lists: when that stage built lists behind itself (grouped launch, threshold >= 0, SGE_MOVE_PIPELINE_LISTS not 0; info[1] = 1)
+   they are the ones the NEXT move stage over the same range, threshold and cap would consume, built from the newest step's costs;
+   otherwise (info[1] = 0) they are the ones the newest stage built at its head, from the costs of the step before, and consumed itself.
+   counts[4] = listed in the order list, listed heavy, heavy demand (cost > threshold, whatever the cap), the range's evaluations;
+   order[count] = the grouped launch's characters, most expensive cost class first (counts[0] entries are valid, the rest -1);
+   heavy[count] = the multi-wave launch's characters (counts[1] valid entries, the rest -1); cost[count] = per-character distance
+   evaluations of the newest step (sge_move_cost_read); info[4] = the cap the heavy list was cut at, the flag above, the threshold the
+   lists were built with, 0. order, heavy, cost and info may be NULL. */
+int sge_debug_move_schedule(sge_context* ctx, int32_t first, int32_t count, int32_t* counts, int32_t* order, int32_t* heavy,
+                            int32_t* cost, int32_t* info);
 
 /* ------------------------------------------------------------------------- */
 /* Skinned-geometry acceleration structures — the step after skinning:        */

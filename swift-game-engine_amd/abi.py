@@ -308,6 +308,7 @@ PROTOTYPES = {
     "sge_move_cost_read": (C.c_int, [VP, C.c_int32, C.c_int32, VP]),
     "sge_debug_wave_profile": (C.c_int, [VP, VP, C.c_int32]),
     "sge_debug_move_lists": (C.c_int, [VP, VP, VP]),
+    "sge_debug_move_schedule": (C.c_int, [VP, i32, i32, VP, VP, VP, VP, VP]),
     "sge_debug_separation": (C.c_int, [VP, VP]),
     "sge_debug_skin_form": (C.c_int, [VP, P(i32), P(i32)]),
     "sge_debug_skin_launch_times": (C.c_int, [VP, VP, i32, P(i32)]),
@@ -467,10 +468,17 @@ def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), os.environ.get("SGE_AMD_LIB", LIB_NAME))
 
 
+# Entries that read the HIP library's own device-side state (the move stage's scheduling lists): a library bound under another prefix
+# (the CPU oracle of the tests, which has no schedule) is not asked for them.
+PRODUCT_ONLY = frozenset({"sge_debug_move_schedule"})
+
+
 def bind(lib, prefix="sge_", names=None):
     """Attach restype/argtypes for every declared symbol (raises AttributeError if one is missing)."""
     for name, (res, args) in PROTOTYPES.items():
         if names is not None and name not in names:
+            continue
+        if prefix != "sge_" and name in PRODUCT_ONLY:
             continue
         fn = getattr(lib, prefix + name[len("sge_"):])
         fn.restype = res

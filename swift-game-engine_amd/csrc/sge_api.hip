@@ -1770,7 +1770,7 @@ int sge_characters_resize(sge_context* c, int32_t count) {
     SGE_ZALLOC(c->dPoseIn[0], N * sizeof(PoseInput));
     SGE_ZALLOC(c->dPoseIn[1], N * sizeof(PoseInput));
     c->palRead = 0;
-    c->listsValid = false;
+    c->listsValid = false; c->listsCount = 0; // (no move stage has run on this crowd: sge_debug_move_schedule)
     SGE_ZALLOC(c->dMoveScratch, N * (size_t)kMoveScratchBytes);
     SGE_ZALLOC(c->dCost, N * sizeof(int));
     SGE_ZALLOC(c->dHint, N);
@@ -3030,6 +3030,35 @@ int sge_debug_move_lists(sge_context* c, int32_t* lists, int32_t* counts) {
     { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
     SGE_HIP(hipMemcpy(lists, c->dLists.p, (size_t)c->crowd.count * 8, hipMemcpyDeviceToHost));
     SGE_HIP(hipMemcpy(counts, c->dListCounts.p, 8, hipMemcpyDeviceToHost));
+    return SGE_OK;
+}
+
+// diagnostics: the scheduling state of the newest move stage as it stands in device memory (include/sge_amd.h says whose lists
+// these are); a drain of every stream and copies, no kernel. The heavy list lies at lists[count..] of the stage's OWN count.
+// (SGE_MOVE_GROUP=0 builds no order list: counts[0] stays 0)
+int sge_debug_move_schedule(sge_context* c, int32_t first, int32_t count, int32_t* counts, int32_t* order, int32_t* heavy,
+                            int32_t* cost, int32_t* info) {
+    if (c && count == 0) { first = 0; count = c->crowd.count; }
+    SGE_RANGE_CHECK();
+    if (!counts) return SGE_ERR_INVALID;
+    if (count == 0 || c->listsCount == 0 || first != c->listsFirst || count != c->listsCount) {
+        set_error("sge_debug_move_schedule: not the range of the newest move stage");
+        return SGE_ERR_STATE;
+    }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    SGE_HIP(hipMemcpy(counts, c->dListCounts.p, 4 * sizeof(int), hipMemcpyDeviceToHost));
+    const int listed = std::max(0, std::min(counts[0], count)), listedHeavy = std::max(0, std::min(counts[1], count));
+    if (order) {
+        for (int i = 0; i < count; ++i) order[i] = -1;
+        if (listed > 0) SGE_HIP(hipMemcpy(order, c->dLists.as<int>(), (size_t)listed * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (heavy) {
+        for (int i = 0; i < count; ++i) heavy[i] = -1;
+        if (listedHeavy > 0) SGE_HIP(hipMemcpy(heavy, c->dLists.as<int>() + count, (size_t)listedHeavy * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (cost) SGE_HIP(hipMemcpy(cost, c->dCost.as<int>() + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    if (info) { info[0] = c->listsCap; info[1] = c->listsValid ? 1 : 0; info[2] = c->listsThreshold; info[3] = 0; }
     return SGE_OK;
 }
 

@@ -729,6 +729,19 @@ class CharacterEngine:
         self._call("move_cost_read", int(first), int(count), ptr(out))
         return out
 
+    def move_schedule(self, first=0, count=0):
+        """The scheduling state of the newest move stage, which must have covered [first, first + count) (count 0: the whole crowd),
+        read after a drain of the context's streams (product only): dict with counts (listed in the order list, listed heavy, heavy
+        demand, evaluations), order and heavy (the valid entries of either list), cost (per character of the range), cap, threshold
+        and built_for_next (True: the lists the next stage over this range would consume, built from `cost`; False: the ones the
+        newest stage built from the costs of the step before and consumed itself)."""
+        n = int(count) if count else self.count
+        counts, info = np.zeros(4, np.int32), np.zeros(4, np.int32)
+        order, heavy, cost = (np.zeros(n, np.int32) for _ in range(3))
+        self._call("debug_move_schedule", int(first), int(count), ptr(counts), ptr(order), ptr(heavy), ptr(cost), ptr(info))
+        return {"counts": counts, "order": order[: max(0, min(int(counts[0]), n))], "heavy": heavy[: max(0, min(int(counts[1]), n))],
+                "cost": cost, "cap": int(info[0]), "built_for_next": bool(info[1]), "threshold": int(info[2])}
+
     def move_stats(self, reset=True):
         st = abi.MoveStats()
         self._call("move_stats_read", C.byref(st), int(reset))
