@@ -122,14 +122,35 @@ def entity_matrix(e):
                            "scale": np.asarray(e["scale"], np.float32)})
 
 
-def scene_upload(engine, world):
+def procedural_textures():
+    """Three small procedural textures in numpy (the idea of the reference's ProceduralTextures: a checkerboard for the ground, a
+    tinted weave and a bump pattern for the player) -> {slot: (rgba uint8 [H][W][4], srgb)}."""
+    yy, xx = np.mgrid[0:64, 0:64]
+    cell = ((xx // 8 + yy // 8) % 2).astype(bool)
+    grain = ((xx * 7 + yy * 13) % 5).astype(np.int32) - 2
+    ground = np.full((64, 64, 4), 255, np.uint8)
+    ground[..., :3] = np.clip(np.where(cell[..., None], (225, 225, 215), (95, 105, 100)) + 3 * grain[..., None], 0, 255)
+    yy, xx = np.mgrid[0:32, 0:32]
+    weave = 0.5 + 0.5 * np.sin(xx * np.pi / 4) * np.sin(yy * np.pi / 4)
+    cloth = np.full((32, 32, 4), 255, np.uint8)
+    cloth[..., :3] = np.rint(255 * (0.55 + 0.45 * weave[..., None] * np.array([1.0, 0.9, 0.8])))
+    nx, ny = 0.35 * np.cos(xx * np.pi / 4) * np.sin(yy * np.pi / 4), 0.35 * np.sin(xx * np.pi / 4) * np.cos(yy * np.pi / 4)
+    n = np.stack([nx, ny, np.ones_like(nx)], -1)
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    bumps = np.full((32, 32, 4), 255, np.uint8)
+    bumps[..., :3] = np.rint((n * 0.5 + 0.5) * 255)
+    return {0: (ground, True), 1: (cloth, True), 2: (bumps, False)}
+
+
+def scene_upload(engine, world, textures=False):
     """The static items of RayTracingScene.buildGeometryBuffers as scene meshes and instances: mesh 0 the ground plane, mesh 1 the
     mirror's render mesh (placed like its hulls), mesh 2 the platform box, instanced twice. -> index of the first platform instance"""
     z = np.load(os.path.join(sge.assets.GOLDEN_DIR, "ornate_mirror_static.npz"))
     ground, hull, plats = world[0], world[1], [e for e in world if e.get("platform")]
     for mesh, (pos, idx) in enumerate(((ground["positions"], ground["indices"]), (z["positions"], z["indices"]), (plats[0]["positions"], plats[0]["indices"]))):
         pos = np.asarray(pos, np.float32).reshape(-1, 3)
-        engine.scene_mesh_upload(mesh, pos, vertex_normals(pos, idx), np.tile(np.array([1, 0, 0, 1], np.float32), (len(pos), 1)), idx)
+        uvs = np.ascontiguousarray(pos[:, [0, 2]] / 4.0) if textures and mesh == 0 else None   # the ground: one checker tile per 4 units
+        engine.scene_mesh_upload(mesh, pos, vertex_normals(pos, idx), np.tile(np.array([1, 0, 0, 1], np.float32), (len(pos), 1)), idx, uvs=uvs)
     items = [(0, ground), (1, hull)] + [(2, e) for e in plats]
     scene_upload.items = [(z["positions"] if m == 1 else e["positions"], e) for m, e in items]   # what shaded_image frames
     engine.scene_instances([m for m, _ in items], np.stack([entity_matrix(e) for _, e in items]))
@@ -170,7 +191,7 @@ def render_probe(engine, width=56, height=28, fov_y=0.6, scene=False):
     return h["hit"].reshape(height, width) == 1, h["distance"].reshape(height, width), h
 
 
-def shaded_image(engine, path, width=320, height=200, fov_y=0.9):
+def shaded_image(engine, path, width=320, height=200, fov_y=0.9, textures=False):
     """The shaded frame (include/sge_amd_render.h: raytraceKernel's layers, lights and bounces in one launch) as a binary PPM, from a
     camera of its own that is pulled back until the mirror (a smooth metal: the mirror path), both platforms and the player are in
     view above the ground. -> the AOV records"""
@@ -205,6 +226,13 @@ def shaded_image(engine, path, width=320, height=200, fov_y=0.9):
     engine.render_materials(mats)
     engine.render_static_materials([0, 1] + [2] * (engine.scene_info().staticInstances - 2))
     engine.render_crowd_materials([3])
+    if textures:   # include/sge_amd_render_textures.h: the ground's checkerboard; the player's base colour and normal map
+        for slot, (rgba, srgb) in procedural_textures().items():
+            engine.render_texture_upload(slot, rgba, srgb=srgb)
+        bind = A.default_render_material_textures(4)
+        bind["baseColor"][0] = 0
+        bind["baseColor"][3], bind["normal"][3] = 1, 2
+        engine.render_material_textures(bind)
     light = np.zeros(1, A.render_light_dtype)   # RayTracingRenderer.swift:163-168's default light, from SUN's side
     light["direction"], light["intensity"], light["color"], light["enabled"], light["maxDistance"] = -SUN, 2.6, (1.0, 0.95, 0.85), 1.0, 200.0
     engine.render_lights(light)
@@ -230,9 +258,14 @@ def ascii_depth(mask, dist, shadow=None):
     return "\n".join(rows)
 
 
-def run(engine, steps=600, dt=1.0 / 60.0, log=None, scene=False):
+def run(engine, steps=600, dt=1.0 / 60.0, log=None, scene=False, textures=False):
     ybot, world, platforms, service = build(engine)
-    first_platform = scene_upload(engine, world) if scene else 0
+    first_platform = scene_upload(engine, world, textures) if scene else 0
+    if scene and textures:   # the player's uvs: the mesh's own, or a planar wrap of its bind pose
+        p = np.asarray(engine.mesh["positions"], np.float32).reshape(-1, 3)
+        span = np.maximum(p.max(0) - p.min(0), 1e-6)
+        uvs = engine.mesh.get("uvs")
+        engine.blas_set_uvs(uvs if uvs is not None else np.stack([(p[:, 0] - p[:, 0].min()) / span[0] * 4, (p[:, 1] - p[:, 1].min()) / span[1] * 8], -1))
     trace = []
     for s in range(steps):
         for p in platforms:
@@ -266,6 +299,7 @@ if __name__ == "__main__":
     ap.add_argument("--render", action="store_true", help="shoot primary rays and shadow rays at the whole scene (ground, mirror, platforms, player) after the last step and "
                     "print the depth image with shadowed pixels marked; with --oracle: primary rays at the characters only")
     ap.add_argument("--image", metavar="PATH", help="with --render (GPU library): also write the shaded frame of the scene (ground, mirror, platforms, shadowed player; a wider camera of its own) as a binary PPM")
+    ap.add_argument("--textures", action="store_true", help="with --render --image: a procedural checkerboard (sRGB) on the ground, a base-colour and a normal texture on the player")
     args = ap.parse_args()
     if args.oracle:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -274,7 +308,7 @@ if __name__ == "__main__":
     else:
         eng = sge.CharacterEngine(0)
     scene = args.render and not args.oracle
-    trace, skinned = run(eng, args.steps, log=print, scene=scene)
+    trace, skinned = run(eng, args.steps, log=print, scene=scene, textures=args.textures)
     print("skinned vertices: %d, bounds %s .. %s" % (len(skinned), skinned.min(0).round(3), skinned.max(0).round(3)))
     if scene:
         mask, dist, hits, shadow = render_probe(eng, scene=True)
@@ -283,7 +317,7 @@ if __name__ == "__main__":
             mask.sum(), mask.size, (ids < A.SCENE_STATIC_BASE).sum(), (ids >= A.SCENE_STATIC_BASE).sum(), shadow.sum(), dist[mask].min(), dist[mask].max()))
         print(ascii_depth(mask, dist, shadow))
         if args.image:
-            aov = shaded_image(eng, args.image)
+            aov = shaded_image(eng, args.image, textures=args.textures)
             ids = aov["instance"]
             print("shaded frame %s: %d x %d, %d queries; pixels: %d ground, %d mirror (%d through the mirror path), %d platforms, %d player, %d with the sun shadowed" % (
                 args.image, aov.shape[1], aov.shape[0], aov["queries"].sum(), (ids == A.SCENE_STATIC_BASE).sum(), (ids == A.SCENE_STATIC_BASE + 1).sum(),

@@ -9,8 +9,10 @@
  * the pixel's chain of queries stays on the device.
  *
  * Two omissions.
- *  1. No textures. The kernel behaves as the reference does with frame.textureCount == 0: every `...TexIndex < textureCount` test
- *     is false, so a material is its factors (:143-150) and the shading normal N is the geometric normal (:267-268).
+ *  1. No textures in this header. On its own the kernel behaves as the reference does with frame.textureCount == 0: every
+ *     `...TexIndex < textureCount` test is false, so a material is its factors (:143-150) and the shading normal N is the
+ *     geometric normal (:267-268). sge_amd_render_textures.h adds the texture slots, the per-material texture indices and the
+ *     sampling sites of the text; while no material binds a slot that holds a texture, the frame is the one described here.
  *  2. No specular IBL. eval_spec_ibl (:88-104, :379) contributes 0; the environment cube, the BRDF table and a sampler that could
  *     be held to a reference are not part of this header.
  * Everything else is the text: maxLayers = 3 with the accumAlpha < 0.99 cut; shadow_bias; every enabled light, skipped when

@@ -447,6 +447,42 @@ RENDER_PROTOTYPES = {
 }
 
 
+# include/sge_amd_render_textures.h: textures in the shaded frame (the pinned bilinear sampler, sample_material, sample_alpha, the
+# normal map).
+class RenderMaterialTextures(C.Structure):
+    _fields_ = [("baseColor", i32), ("normal", i32), ("metallicRoughness", i32), ("emissive", i32), ("occlusion", i32),
+                ("normalScale", f32), ("pad", i32 * 2)]
+
+
+assert C.sizeof(RenderMaterialTextures) == 32
+render_material_textures_dtype = np.dtype([("baseColor", "<i4"), ("normal", "<i4"), ("metallicRoughness", "<i4"), ("emissive", "<i4"),
+                                           ("occlusion", "<i4"), ("normalScale", "<f4"), ("pad", "<i4", 2)])
+assert render_material_textures_dtype.itemsize == 32
+SGE_MAX_RENDER_TEXTURES = 32
+TEX_RGBA8_UNORM, TEX_RGBA8_UNORM_SRGB = 0, 1
+SGE_MAX_TEXTURE_DIM = 8192
+
+
+def default_render_material_textures(count=1):
+    """No texture anywhere, normalScale 1 (Material.swift:46): the state of a fresh context."""
+    t = np.zeros(count, render_material_textures_dtype)
+    for f in ("baseColor", "normal", "metallicRoughness", "emissive", "occlusion"):
+        t[f] = -1
+    t["normalScale"] = 1.0
+    return t
+
+
+RENDER_TEXTURE_PROTOTYPES = {
+    "sge_render_texture_upload": (C.c_int, [VP, i32, i32, i32, i32, VP]),
+    "sge_render_texture_clear": (C.c_int, [VP, i32]),
+    "sge_render_material_textures_set": (C.c_int, [VP, i32, VP]),
+    "sge_render_texture_info_get": (C.c_int, [VP, i32, P(i32), P(i32), P(i32)]),
+    "sge_render_srgb_table_get": (C.c_int, [VP, VP]),
+    "sge_render_texture_sample_batch": (C.c_int, [VP, i32, VP, i32, VP]),
+    "sge_render_texture_sample_device": (C.c_int, [VP, i32, VP, i32, VP]),
+}
+
+
 # include/sge_amd_variant_scene.h: a crowd with mesh variants in the ray scene and the shaded frame.
 class SceneCrowdStatus(C.Structure):
     _fields_ = [("crowdReady", i32), ("ragged", i32), ("reason", i32), ("variant", i32)]
@@ -500,7 +536,8 @@ def load_library(path=None):
         raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = bind(C.CDLL(path))
-    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES, RENDER_PROTOTYPES, VARIANT_SCENE_PROTOTYPES):
+    for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES, RENDER_PROTOTYPES, VARIANT_SCENE_PROTOTYPES,
+                  RENDER_TEXTURE_PROTOTYPES):
         for name, (res, args) in table.items():  # (raises AttributeError if one is missing)
             fn = getattr(lib, name)
             fn.restype = res

@@ -182,6 +182,12 @@ struct sge_context {
     struct RenderStage { void* host = nullptr; hipEvent_t copied = nullptr; bool inFlight = false; } renderStage[2];
     int renderStageSlot = 0;
     DevBuf dRenderMaterials, dRenderStaticMaterial, dRenderCrowdMaterial, dRenderLights, dRenderArgs, dRenderRGBA, dRenderAOV;
+    // textures (include/sge_amd_render_textures.h): the slots, the bindings as set (materials beyond them: none), and the device
+    // copies the textured kernels read: the slot table, the bindings resolved against the slots that hold a texture, the sRGB table
+    struct RenderTexture { DevBuf texels; int width = 0, height = 0, format = 0; } renderTextures[SGE_MAX_RENDER_TEXTURES];
+    std::vector<sge_render_material_textures> hostMaterialTextures;
+    bool renderTextured = false; // some bound slot holds a texture: the frame runs the textured kernels
+    DevBuf dRenderTexTable, dRenderBindings, dRenderSrgb, dTexSampleUV, dTexSampleRGBA;
     // stats / profiling
     DevBuf dStats, dWaveProf, dOrderHist, dSepAgents, dSepCounts, dSepFlow;
     int separationIterations = 2; float separationMargin = 0.2f, separationHeightMargin = 0.1f; // AgentSeparationSystem.init :2146-2152
@@ -828,6 +834,57 @@ int uploadRenderMaterials(sge_context* c) {
     SGE_HIP(hipStreamSynchronize(c->stream));
     return SGE_OK;
 }
+// ---- textures (include/sge_amd_render_textures.h) ----
+// the decode table of the header: double, rounded to float32
+const float* srgbTable() {
+    struct Table { float v[256]; };
+    static const Table table = [] { // (initialised once, under the language's guard for function-local statics)
+        Table t;
+        for (int c = 0; c < 256; ++c) {
+            const double v = c / 255.0;
+            t.v[c] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4));
+        }
+        return t;
+    }();
+    return table.v;
+}
+constexpr sge_render_material_textures kNoTextures{-1, -1, -1, -1, -1, 1.0f, {0, 0}};
+// The device copies behind a change of a slot or of the bindings: the slot table, the bindings with every index that names no
+// texture turned into -1, the sRGB table. Says whether any binding is left. The caller has drained the device.
+int uploadRenderTextures(sge_context* c) {
+    DevRenderTexture table[SGE_MAX_RENDER_TEXTURES] = {};
+    for (int i = 0; i < SGE_MAX_RENDER_TEXTURES; ++i) {
+        const sge_context::RenderTexture& t = c->renderTextures[i];
+        if (t.width > 0) table[i] = DevRenderTexture{t.texels.as<uint32_t>(), t.width, t.height, t.format, 0};
+    }
+    std::vector<sge_render_material_textures> dev(SGE_MAX_RENDER_MATERIALS, kNoTextures);
+    bool any = false;
+    auto resolve = [&](int32_t idx) {
+        const bool ok = idx >= 0 && idx < SGE_MAX_RENDER_TEXTURES && c->renderTextures[idx].width > 0;
+        any = any || ok;
+        return ok ? idx : (int32_t)-1;
+    };
+    for (size_t i = 0; i < c->hostMaterialTextures.size(); ++i) {
+        const sge_render_material_textures& b = c->hostMaterialTextures[i];
+        dev[i] = sge_render_material_textures{resolve(b.baseColor), resolve(b.normal), resolve(b.metallicRoughness), resolve(b.emissive),
+                                              resolve(b.occlusion), b.normalScale, {0, 0}};
+    }
+    int rc;
+    if ((rc = upload(c->dRenderTexTable, table, sizeof(table), c->stream)) != SGE_OK) return rc;
+    if ((rc = upload(c->dRenderBindings, dev.data(), dev.size() * sizeof(dev[0]), c->stream)) != SGE_OK) return rc;
+    if (!c->dRenderSrgb.p && (rc = upload(c->dRenderSrgb, srgbTable(), 256 * sizeof(float), c->stream)) != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    c->renderTextured = any;
+    return SGE_OK;
+}
+int enqueueTextureSample(sge_context* c, int32_t slot, const float* d_uvs, int32_t count, float* d_rgba) {
+    // (the slot holds a texture, so an upload has made the device copy of the sRGB table)
+    const sge_context::RenderTexture& t = c->renderTextures[slot];
+    launch_texture_sample(DevRenderTexture{t.texels.as<uint32_t>(), t.width, t.height, t.format, 0}, c->dRenderSrgb.as<float>(), d_uvs, count, d_rgba, c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+
 // An assignment lives until the list it assigns is replaced: sge_scene_instances_set (another count, or another device list) and
 // sge_characters_resize (another count) are observed here, by every sge_render_* entry before it does anything else, and the
 // assignment is dropped for good: a later list of the old length starts from material 0 again.
@@ -872,12 +929,15 @@ int enqueueRenderFrame(sge_context* c, const sge_render_frame* f, float* d_rgba,
     A.R.lights = c->dRenderLights.as<DevRenderLight>();
     A.R.rgba = d_rgba;
     A.R.aov = d_aov;
+    const bool textured = c->renderTextured;
+    if (textured) A.X = RenderTextures{c->dRenderTexTable.as<DevRenderTexture>(), c->dRenderBindings.as<sge_render_material_textures>(), c->dRenderSrgb.as<float>()};
     RenderArgs* d_args = c->dRenderArgs.as<RenderArgs>() + slot;
     SGE_HIP(hipMemcpyAsync(d_args, st.host, sizeof(RenderArgs), hipMemcpyHostToDevice, c->stream));
     SGE_HIP(hipEventRecord(st.copied, c->stream));
     st.inFlight = true;
-    if (ragged) launch_render_frame_ragged(A, d_args, c->stream);
-    else launch_render_frame(A, d_args, c->stream);
+    // the textured kernels only when a bound slot holds a texture: every other frame is the frame of sge_amd_render.h
+    if (ragged) (textured ? launch_render_frame_ragged_textured : launch_render_frame_ragged)(A, d_args, c->stream);
+    else (textured ? launch_render_frame_textured : launch_render_frame)(A, d_args, c->stream);
     SGE_HIP(hipGetLastError());
     return SGE_OK;
 }
@@ -997,6 +1057,8 @@ void sge_context_destroy(sge_context* c) {
     for (auto& st : c->sceneStage) { if (st.host) (void)hipHostFree(st.host); if (st.copied) (void)hipEventDestroy(st.copied); }
     for (auto& st : c->renderStage) { if (st.host) (void)hipHostFree(st.host); if (st.copied) (void)hipEventDestroy(st.copied); }
     for (DevBuf* b : {&c->dRenderMaterials, &c->dRenderStaticMaterial, &c->dRenderCrowdMaterial, &c->dRenderLights, &c->dRenderArgs, &c->dRenderRGBA, &c->dRenderAOV}) b->release();
+    for (DevBuf* b : {&c->dRenderTexTable, &c->dRenderBindings, &c->dRenderSrgb, &c->dTexSampleUV, &c->dTexSampleRGBA}) b->release();
+    for (auto& t : c->renderTextures) t.texels.release();
     for (DevBuf* b : {&c->dVariantTable, &c->dVariantOf, &c->dVariantSnap[0], &c->dVariantSnap[1], &c->dVertexOff, &c->dVariantLists, &c->dSkinPlan}) b->release();
     for (hipEvent_t e : {c->evVariantSnap, c->evPlanDone[0], c->evPlanDone[1], c->variantStage[0].copied, c->variantStage[1].copied}) if (e) (void)hipEventDestroy(e);
     for (auto& st : c->variantStage) if (st.host) (void)hipHostFree(st.host);
@@ -2857,6 +2919,88 @@ int sge_render_frame_device(sge_context* c, const struct sge_render_frame* frame
     (void)hipSetDevice(c->device);
     { int rcj = joinSkin(c); if (rcj != SGE_OK) return rcj; }
     return enqueueRenderFrame(c, frame, reinterpret_cast<float*>(d_rgba), reinterpret_cast<sge_render_aov*>(d_aov));
+}
+
+// ---- textures in the shaded frame (include/sge_amd_render_textures.h) ----
+int sge_render_texture_upload(sge_context* c, int32_t slot, int32_t width, int32_t height, int32_t format, const uint8_t* rgba) {
+    if (!c || !rgba) { set_error("sge_render_texture_upload: bad argument"); return SGE_ERR_INVALID; }
+    if (slot < 0 || slot >= SGE_MAX_RENDER_TEXTURES) { set_error("sge_render_texture_upload: slot outside 0 .. SGE_MAX_RENDER_TEXTURES - 1"); return SGE_ERR_INVALID; }
+    if (width < 1 || height < 1 || width > SGE_MAX_TEXTURE_DIM || height > SGE_MAX_TEXTURE_DIM) { set_error("sge_render_texture_upload: dimension outside 1 .. SGE_MAX_TEXTURE_DIM"); return SGE_ERR_INVALID; }
+    if (format != SGE_TEX_RGBA8_UNORM && format != SGE_TEX_RGBA8_UNORM_SRGB) { set_error("sge_render_texture_upload: unknown format"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    // into a buffer of its own first: a failed allocation leaves the slot as it was
+    DevBuf fresh;
+    int rc = upload(fresh, rgba, (size_t)width * height * 4, c->stream);
+    if (rc == SGE_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("sge_render_texture_upload: the copy failed"); rc = SGE_ERR_DEVICE; }
+    if (rc != SGE_OK) { fresh.release(); return rc; }
+    sge_context::RenderTexture& t = c->renderTextures[slot];
+    t.texels.release();
+    t.texels = fresh;
+    t.width = width; t.height = height; t.format = format;
+    return uploadRenderTextures(c);
+}
+
+int sge_render_texture_clear(sge_context* c, int32_t slot) {
+    if (!c || slot < -1 || slot >= SGE_MAX_RENDER_TEXTURES) { set_error("sge_render_texture_clear: bad argument (slot -1 .. SGE_MAX_RENDER_TEXTURES - 1)"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    for (int i = 0; i < SGE_MAX_RENDER_TEXTURES; ++i) {
+        if (slot >= 0 && i != slot) continue;
+        sge_context::RenderTexture& t = c->renderTextures[i];
+        t.texels.release();
+        t.width = t.height = t.format = 0;
+    }
+    return uploadRenderTextures(c);
+}
+
+int sge_render_material_textures_set(sge_context* c, int32_t count, const struct sge_render_material_textures* table) {
+    if (!c || !table || count < 1 || count > SGE_MAX_RENDER_MATERIALS) { set_error("sge_render_material_textures_set: bad argument (1 .. SGE_MAX_RENDER_MATERIALS entries)"); return SGE_ERR_INVALID; }
+    for (int i = 0; i < count; ++i)
+        if (!std::isfinite(table[i].normalScale)) { set_error("sge_render_material_textures_set: a normalScale is not finite"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    const std::vector<sge_render_material_textures> before = c->hostMaterialTextures;
+    c->hostMaterialTextures.assign(table, table + count);
+    const int rc = uploadRenderTextures(c);
+    if (rc != SGE_OK) c->hostMaterialTextures = before;
+    return rc;
+}
+
+int sge_render_texture_info_get(sge_context* c, int32_t slot, int32_t* width, int32_t* height, int32_t* format) {
+    if (!c || !width || !height || !format || slot < 0 || slot >= SGE_MAX_RENDER_TEXTURES) { set_error("sge_render_texture_info_get: bad argument"); return SGE_ERR_INVALID; }
+    const sge_context::RenderTexture& t = c->renderTextures[slot];
+    *width = t.width; *height = t.height; *format = t.format;
+    return SGE_OK;
+}
+
+int sge_render_srgb_table_get(sge_context* c, float table[256]) {
+    if (!c || !table) { set_error("sge_render_srgb_table_get: bad argument"); return SGE_ERR_INVALID; }
+    std::memcpy(table, srgbTable(), 256 * sizeof(float));
+    return SGE_OK;
+}
+
+int sge_render_texture_sample_batch(sge_context* c, int32_t slot, const float* uvs, int32_t count, float* rgba) {
+    if (!c || count < 0 || (count > 0 && (!uvs || !rgba)) || slot < 0 || slot >= SGE_MAX_RENDER_TEXTURES) { set_error("sge_render_texture_sample_batch: bad argument"); return SGE_ERR_INVALID; }
+    if (c->renderTextures[slot].width == 0) { set_error("sge_render_texture_sample_batch: the slot holds no texture"); return SGE_ERR_STATE; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    int rc;
+    if ((rc = upload(c->dTexSampleUV, uvs, (size_t)count * 8, c->stream)) != SGE_OK) return rc;
+    if ((rc = c->dTexSampleRGBA.alloc((size_t)count * 16)) != SGE_OK) return rc;
+    if ((rc = enqueueTextureSample(c, slot, c->dTexSampleUV.as<float>(), count, c->dTexSampleRGBA.as<float>())) != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    SGE_HIP(hipMemcpy(rgba, c->dTexSampleRGBA.p, (size_t)count * 16, hipMemcpyDeviceToHost));
+    return SGE_OK;
+}
+
+int sge_render_texture_sample_device(sge_context* c, int32_t slot, const void* d_uvs, int32_t count, void* d_rgba) {
+    if (!c || count < 0 || (count > 0 && (!d_uvs || !d_rgba)) || slot < 0 || slot >= SGE_MAX_RENDER_TEXTURES) { set_error("sge_render_texture_sample_device: bad argument"); return SGE_ERR_INVALID; }
+    if (c->renderTextures[slot].width == 0) { set_error("sge_render_texture_sample_device: the slot holds no texture"); return SGE_ERR_STATE; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    return enqueueTextureSample(c, slot, reinterpret_cast<const float*>(d_uvs), count, reinterpret_cast<float*>(d_rgba));
 }
 
 int sge_blas_profile_read(sge_context* c, double* ms, int64_t* launches, int reset) {

@@ -9,6 +9,7 @@
 #include "../../include/sge_amd_variant_blas.h"
 #include "../../include/sge_amd_ray_scene.h"
 #include "../../include/sge_amd_render.h"
+#include "../../include/sge_amd_render_textures.h"
 #include "../../include/sge_amd_variant_scene.h"
 #include "sge_math.hpp"
 
@@ -31,6 +32,7 @@ static_assert(sizeof(struct sge_blas_variant_layout) == 48, "layout");
 static_assert(sizeof(struct sge_scene_info) == 16, "layout");
 static_assert(sizeof(struct sge_render_material) == 48 && sizeof(struct sge_render_light) == 48, "layout");
 static_assert(sizeof(struct sge_render_frame) == 204 && sizeof(struct sge_render_aov) == 32, "layout");
+static_assert(sizeof(struct sge_render_material_textures) == 32, "layout");
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
@@ -512,8 +514,22 @@ struct RenderLaunch {
 // One wavefront per pixel. The kernel reads both records from device memory: `d_args` holds a copy of `host` (S as
 // launch_scene_trace takes it), made on `s` before the launch.
 // (G: behind the two records the uniform kernel reads; filled and read only when the crowd has mesh variants)
-struct RenderArgs { SceneTrace S; RenderLaunch R; SceneRagged G; };
+// Textures (include/sge_amd_render_textures.h). A slot: packed rgba8 words, row 0 first; texels null: the slot is empty.
+struct DevRenderTexture { const uint32_t* texels; int width, height, format, _pad; };
+struct RenderTextures {
+    const DevRenderTexture* table;                // device [SGE_MAX_RENDER_TEXTURES]
+    const sge_render_material_textures* bindings; // device [SGE_MAX_RENDER_MATERIALS], resolved by the host: an index is a slot that
+                                                  // holds a texture, or -1
+    const float* srgb;                            // device [256]: the decode table of the header
+};
+// (X: behind the records the untextured kernels read; filled and read only when a bound slot holds a texture)
+struct RenderArgs { SceneTrace S; RenderLaunch R; SceneRagged G; RenderTextures X; };
 void launch_render_frame(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
 void launch_render_frame_ragged(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
+// the textured forms of the two (render_textured_kernel, render_ragged_textured_kernel)
+void launch_render_frame_textured(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
+void launch_render_frame_ragged_textured(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
+// the sampler alone: rgba[n][4] = tex at uvs[n][2] (device arrays), one thread per sample
+void launch_texture_sample(const DevRenderTexture& tex, const float* srgb, const float* d_uvs, int n, float* d_rgba, hipStream_t s);
 
 } // namespace sge

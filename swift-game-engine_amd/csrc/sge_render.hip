@@ -1,5 +1,5 @@
 // The shaded frame for gfx950 (include/sge_amd_render.h): raytraceKernel (RayTracing.metalinc:197-730) over the ray scene, with
-// frame.textureCount == 0 and without specular IBL.
+// frame.textureCount == 0 and without specular IBL; and its textured form (include/sge_amd_render_textures.h).
 //
 // render_frame_kernel — one wavefront per pixel, plain launch, the LDS traversal stack and the closest-hit walk of
 // scene_trace_kernel (sge_ray_scene_dev.hpp, sge_blas_trace_dev.hpp). The reference inlines its intersector at seven call sites
@@ -16,6 +16,14 @@
 // (three layers; the layer's ray and light 0's walk, the same for the mirror bounce, the refraction ray and a walk per light),
 // the light loop runs at most lights + 1 times per pass.
 //
+// Textures. render_textured_kernel is the same text with TEX = true (sge_render_frame_body.inc): at a surface it takes the hit
+// record's uv and shading frame (blasHitRecord, wave-uniformly: the winner's barycentrics are made scalar too), runs
+// sample_material and the normal map through texSample (sge_render_dev.hpp) and keeps the sampled surface, 48 bytes, in the
+// pixel's LDS state for the light loop, the mirror test, the mixes and the compositing; an occluder of a shadow walk gets
+// sample_alpha. All 64 lanes hold the same surface, so every texel address is wave-uniform: four loads per sample, no lanes
+// spread over taps. The host launches it only when a bound slot holds a texture; render_frame_kernel is untouched by it (its
+// own kernel, its own name: the register figures of the untextured frame are what they were).
+//
 // Built with -ffp-contract=off: what decides a ray is the float32 expression the header pins, as written.
 #include "sge_render_dev.hpp"
 
@@ -26,7 +34,25 @@ namespace sge {
 template <int STRIDE>
 __global__ __launch_bounds__(kWave) void render_frame_kernel(const RenderArgs* A) {
     const UniformCrowd<STRIDE> C{A->S.T};
+    constexpr bool TEX = STRIDE == 0; // false (a constant that depends on STRIDE: see the body)
 #include "sge_render_frame_body.inc"
+}
+
+template <int STRIDE>
+__global__ __launch_bounds__(kWave) void render_textured_kernel(const RenderArgs* A) {
+    const UniformCrowd<STRIDE> C{A->S.T};
+    constexpr bool TEX = STRIDE != 0; // true
+#include "sge_render_frame_body.inc"
+}
+
+// the sampler alone (sge_render_texture_sample_*): one thread per sample through the frame kernels' texSample
+__global__ __launch_bounds__(256) void texture_sample_kernel(DevRenderTexture tex, const float* srgb, const float* uvs, int n, float* rgba) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float c[4];
+    texSample(tex, srgb, uvs[(size_t)i * 2], uvs[(size_t)i * 2 + 1], c);
+    float* o = rgba + (size_t)i * 4;
+    o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[3];
 }
 
 void launch_render_frame(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s) {
@@ -34,6 +60,18 @@ void launch_render_frame(const RenderArgs& host, const RenderArgs* d_args, hipSt
     if (n <= 0) return;
     if (host.S.crowd && host.S.T.layout == SGE_LAYOUT_PADDED16) hipLaunchKernelGGL((render_frame_kernel<4>), dim3(n), dim3(kWave), 0, s, d_args);
     else hipLaunchKernelGGL((render_frame_kernel<3>), dim3(n), dim3(kWave), 0, s, d_args);
+}
+
+void launch_render_frame_textured(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s) {
+    const int n = host.R.frame.width * host.R.frame.height;
+    if (n <= 0) return;
+    if (host.S.crowd && host.S.T.layout == SGE_LAYOUT_PADDED16) hipLaunchKernelGGL((render_textured_kernel<4>), dim3(n), dim3(kWave), 0, s, d_args);
+    else hipLaunchKernelGGL((render_textured_kernel<3>), dim3(n), dim3(kWave), 0, s, d_args);
+}
+
+void launch_texture_sample(const DevRenderTexture& tex, const float* srgb, const float* d_uvs, int n, float* d_rgba, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(texture_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tex, srgb, d_uvs, n, d_rgba);
 }
 
 } // namespace sge

@@ -92,13 +92,150 @@ __device__ __forceinline__ F3 hitNormal(const SceneTrace& S, const Crowd& C, int
     return blasFaceNormal(M, arr3(a), arr3(b), arr3(c), wd);
 }
 
-// what a pixel carries from query to query (see the kernel)
-struct PixelState {
+// ---- textures (include/sge_amd_render_textures.h) ----
+
+// a float every lane holds, as a scalar
+__device__ __forceinline__ float uniformFloat(float v) { return __uint_as_float((unsigned)uniformInt((int)__float_as_uint(v))); }
+
+// The pinned sampler: clamp-to-edge, level 0, bilinear, decode before filtering. Four plain loads of packed words; in the frame
+// kernels every lane of the pixel's wavefront asks for the same uv, so the addresses are wave-uniform.
+__device__ __forceinline__ void texDecode(uint32_t w, bool srgb, const float* table, float out[4]) {
+    const uint32_t r = w & 255u, g = (w >> 8) & 255u, b = (w >> 16) & 255u, a = w >> 24;
+    out[0] = srgb ? table[r] : (float)r / 255.0f;
+    out[1] = srgb ? table[g] : (float)g / 255.0f;
+    out[2] = srgb ? table[b] : (float)b / 255.0f;
+    out[3] = (float)a / 255.0f;
+}
+__device__ __forceinline__ void texSample(const DevRenderTexture& t, const float* table, float u, float v, float out[4]) {
+    const int W = t.width, H = t.height;
+    const float x = fminf(fmaxf(u * (float)W - 0.5f, 0.0f), (float)(W - 1));
+    const float y = fminf(fmaxf(v * (float)H - 0.5f, 0.0f), (float)(H - 1));
+    const int x0 = (int)floorf(x), y0 = (int)floorf(y);
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    const float fx = x - (float)x0, fy = y - (float)y0;
+    const bool srgb = t.format == SGE_TEX_RGBA8_UNORM_SRGB;
+    const uint32_t* r0 = t.texels + (size_t)y0 * W;
+    const uint32_t* r1 = t.texels + (size_t)y1 * W;
+    float t00[4], t10[4], t01[4], t11[4];
+    texDecode(r0[x0], srgb, table, t00);
+    texDecode(r0[x1], srgb, table, t10);
+    texDecode(r1[x0], srgb, table, t01);
+    texDecode(r1[x1], srgb, table, t11);
+    for (int k = 0; k < 4; ++k) {
+        const float top = t00[k] * (1.0f - fx) + t10[k] * fx;
+        const float bot = t01[k] * (1.0f - fx) + t11[k] * fx;
+        out[k] = top * (1.0f - fy) + bot * fy;
+    }
+}
+
+// The hit record of sge_scene_intersect_* at a hit the scan reported: blasHitRecord over whichever half's streams hold the
+// triangle, as the tail of sge_scene_trace_body.inc calls it. (u, v) are the barycentrics the walk left.
+template <int STRIDE, class Crowd>
+__device__ __forceinline__ void renderHitRecord(const SceneTrace& S, const Crowd& C, int inst, uint32_t prim, float u, float v, F3 wd, sge_blas_hit& H) {
+    const BlasBest B{0.0f, u, v, prim, inst};
+    H.uv[0] = 0.0f; H.uv[1] = 0.0f;
+    if (inst >= SGE_SCENE_STATIC_BASE) {
+        const int s = inst - SGE_SCENE_STATIC_BASE;
+        const DevSceneMesh& m = S.meshes[S.meshOf[s]];
+        blasHitRecord<3>(loadInstance(S.matrices, s), m.positions, m.normals, m.tangents, m.uvs, m.indices + (size_t)prim * 3, wd, B, H);
+    } else {
+        const BlasTrace& T = S.T;
+        const CrowdStreams cs = C.streams(inst);
+        const size_t vbase = cs.vbase;
+        blasHitRecord<STRIDE>(loadInstance(T.instances, inst), reinterpret_cast<const float*>(T.positions) + vbase * STRIDE,
+                              reinterpret_cast<const float*>(T.normals) + vbase * STRIDE, T.tangents + vbase * 4, cs.uvs,
+                              cs.indices + (size_t)prim * 3, wd, B, H);
+    }
+}
+
+// sample_alpha (RayTracing.metalinc:178-195): the occluder's alpha factor (clamped in the device table) times its texture's w
+template <int STRIDE, class Crowd>
+__device__ __forceinline__ float sampleAlpha(const SceneTrace& S, const RenderLaunch& R, const RenderTextures& X, const Crowd& C, int inst, uint32_t prim,
+                                             float u, float v, F3 wd) {
+    const int mat = materialOf(S, R, inst);
+    float alpha = R.materials[mat].alpha;
+    const int tex = X.bindings[mat].baseColor;
+    if (tex >= 0) {
+        sge_blas_hit H;
+        renderHitRecord<STRIDE>(S, C, inst, prim, u, v, wd, H);
+        float c[4];
+        texSample(X.table[tex], X.srgb, H.uv[0], H.uv[1], c);
+        alpha *= c[3];
+    }
+    return alpha;
+}
+
+// sample_material (:132-176) and the normal map (:283-316) at a surface: `m` is the sampled PBRSample in the fields of the material
+// it starts from, N comes in as the face-forwarded geometric normal and leaves as the shading normal.
+template <int STRIDE, class Crowd>
+__device__ __forceinline__ void sampleSurface(const SceneTrace& S, const RenderLaunch& R, const RenderTextures& X, const Crowd& C, int inst, uint32_t prim,
+                                              float u, float v, F3 wd, sge_render_material& m, F3& N) {
+    const int mat = materialOf(S, R, inst);
+    m = R.materials[mat];
+    const sge_render_material_textures b = X.bindings[mat];
+    if (b.baseColor < 0 && b.normal < 0 && b.metallicRoughness < 0 && b.emissive < 0 && b.occlusion < 0) return;
+    sge_blas_hit H;
+    renderHitRecord<STRIDE>(S, C, inst, prim, u, v, wd, H);
+    const float tu = H.uv[0], tv = H.uv[1];
+    float c[4];
+    if (b.baseColor >= 0) {
+        texSample(X.table[b.baseColor], X.srgb, tu, tv, c);
+        m.baseColor[0] *= c[0]; m.baseColor[1] *= c[1]; m.baseColor[2] *= c[2];
+        m.alpha *= c[3];
+    }
+    if (b.metallicRoughness >= 0) {
+        texSample(X.table[b.metallicRoughness], X.srgb, tu, tv, c);
+        m.roughness *= c[1];
+        m.metallic *= c[2];
+    }
+    if (b.emissive >= 0) {
+        texSample(X.table[b.emissive], X.srgb, tu, tv, c);
+        m.emissive[0] *= c[0]; m.emissive[1] *= c[1]; m.emissive[2] *= c[2];
+    }
+    if (b.occlusion >= 0) {
+        texSample(X.table[b.occlusion], X.srgb, tu, tv, c);
+        m.occlusionStrength *= c[0];
+    }
+    if (b.normal >= 0) {
+        texSample(X.table[b.normal], X.srgb, tu, tv, c);
+        const float nx = c[0] * 2.0f - 1.0f, ny = c[1] * 2.0f - 1.0f;
+        const float NoV = sat(dot(N, unit(-wd)));
+        const float t = sat((NoV - 0.05f) / (0.5f - 0.05f));
+        const float graze = (t * t) * (3.0f - 2.0f * t);
+        const float ns = 4.0f + fmaxf(b.normalScale - 4.0f, 0.0f) * 0.25f;
+        const float x = nx * (ns * graze), y = ny * (ns * graze);
+        const float z = sqrtf(fmaxf(1.0f - (x * x + y * y), 0.0f));
+        F3 n = unit((arr3(H.tangent) * x + arr3(H.bitangent) * y) + arr3(H.normal) * z);
+        if (dot(n, wd) > 0.0f) n = -n;
+        N = n;
+    }
+}
+
+// what a pixel carries from query to query (see the kernel). TEX: the textured form keeps the sampled surfaces (sample_material's
+// PBRSample, in the fields of sge_render_material) where the untextured one keeps the material indices.
+template <bool TEX>
+struct PixelStateT {
     F3 pHit, pN, pd, pColor; float pBias; int pMat;
     F3 sHit, sN, sd, direct, rd; float sBias, shadow; int sMat, li, sCount, pending;
     F3 accum; float accumAlpha; int layer, queries, phase;
     int aInst, aPrim, aFlags; float aDist, aShadow;
 };
+template <>
+struct PixelStateT<true> {
+    F3 pHit, pN, pd, pColor; float pBias; sge_render_material pSurf;
+    F3 sHit, sN, sd, direct, rd; float sBias, shadow; sge_render_material sSurf; int li, sCount, pending;
+    F3 accum; float accumAlpha; int layer, queries, phase;
+    int aInst, aPrim, aFlags; float aDist, aShadow;
+};
+// the surface being shaded / the layer's surface once shaded
+template <bool TEX>
+__device__ __forceinline__ const sge_render_material& surfaceS(const PixelStateT<TEX>& ps, const RenderLaunch& R) {
+    if constexpr (TEX) return ps.sSurf; else return R.materials[ps.sMat];
+}
+template <bool TEX>
+__device__ __forceinline__ const sge_render_material& surfaceP(const PixelStateT<TEX>& ps, const RenderLaunch& R) {
+    if constexpr (TEX) return ps.pSurf; else return R.materials[ps.pMat];
+}
 
 } // namespace
 

@@ -1,7 +1,10 @@
 // One pixel of the frame: the body of render_frame_kernel (sge_render.hip) and of render_ragged_frame_kernel
 // (sge_scene_variants.hip), included inside the kernel (see sge_scene_trace_body.inc for why it is a text and not a function). In
-// scope where it is included: STRIDE (floats per vertex of the crowd's skinned positions), the kernel's argument A, and C, the
-// crowd half's accessor over A->S.T (sge_ray_scene_dev.hpp).
+// scope where it is included: STRIDE (floats per vertex of the crowd's skinned positions), the kernel's argument A, C, the
+// crowd half's accessor over A->S.T (sge_ray_scene_dev.hpp), and TEX, a constant that depends on STRIDE (so that the arm of an
+// `if constexpr (TEX)` that is not taken is discarded unseen): true in the textured kernels (include/sge_amd_render_textures.h),
+// which sample where the text samples and carry the sampled surface; false in the kernels of sge_amd_render.h, which compile to
+// what they were.
     __shared__ int stack[kBlasStack];
     const int lane = threadIdx.x;
     // (the two records are read where they are used, from device memory: as kernel arguments they were held in scalar registers
@@ -10,6 +13,7 @@
     const RenderLaunch& R = A->R;
     const sge_render_frame& F = R.frame;
     const BlasTrace& T = S.T;
+    const RenderTextures& X = A->X; // (read by the textured form only)
     const int W = F.width, H = F.height;
     const int pixel = blockIdx.x;
     if (pixel >= W * H) return;
@@ -37,24 +41,25 @@
     int mode = 0;
     // Everything but the pending query lives in LDS while the scan runs (every lane holds the same values and stores the same
     // words; the scan's barriers keep the compiler from carrying them in registers across it): the registers belong to the walk.
-    __shared__ PixelState ps;
+    __shared__ PixelStateT<TEX> ps;
     // the layer's surface once shaded, kept while a bounce is shaded
     F3 &pHit = ps.pHit, &pN = ps.pN, &pd = ps.pd, &pColor = ps.pColor;
     float& pBias = ps.pBias;
-    int& pMat = ps.pMat;
     // the surface being shaded
     F3 &sHit = ps.sHit, &sN = ps.sN, &sd = ps.sd, &direct = ps.direct, &rd = ps.rd;
     float &sBias = ps.sBias, &shadow = ps.shadow;
-    int &sMat = ps.sMat, &li = ps.li, &sCount = ps.sCount, &pending = ps.pending;
+    int &li = ps.li, &sCount = ps.sCount, &pending = ps.pending;
     // the pixel
     F3& accum = ps.accum;
     float& accumAlpha = ps.accumAlpha;
     int &layer = ps.layer, &queries = ps.queries, &phase = ps.phase;
     int &aInst = ps.aInst, &aPrim = ps.aPrim, &aFlags = ps.aFlags;
     float &aDist = ps.aDist, &aShadow = ps.aShadow;
-    pHit = F3{0, 0, 0}; pN = F3{0, 0, 1}; pd = dir; pColor = F3{0, 0, 0}; pBias = 0; pMat = 0;
+    pHit = F3{0, 0, 0}; pN = F3{0, 0, 1}; pd = dir; pColor = F3{0, 0, 0}; pBias = 0;
+    if constexpr (TEX) ps.pSurf = R.materials[0]; else ps.pMat = 0;
     sHit = F3{0, 0, 0}; sN = F3{0, 0, 1}; sd = dir; direct = F3{0, 0, 0}; rd = dir; sBias = 0; shadow = 1.0f;
-    sMat = 0; li = 0; sCount = 0; pending = 0;
+    if constexpr (TEX) ps.sSurf = R.materials[0]; else ps.sMat = 0;
+    li = 0; sCount = 0; pending = 0;
     accum = F3{0, 0, 0}; accumAlpha = 0; layer = 0; queries = 0; phase = 0;
     aInst = -1; aPrim = -1; aFlags = 0; aDist = 0; aShadow = 1.0f;
 
@@ -99,7 +104,8 @@
         if (mode == 1) { // a step of a shadow walk, :341-371
             bool end = true;
             if (hit) {
-                shadow *= (1.0f - R.materials[materialOf(S, R, hInst)].alpha);
+                if constexpr (TEX) shadow *= (1.0f - sampleAlpha<STRIDE>(S, R, X, C, hInst, hPrim, uniformFloat(best.u), uniformFloat(best.v), qd)); // sample_alpha, :357
+                else shadow *= (1.0f - R.materials[materialOf(S, R, hInst)].alpha);
                 ++sCount;
                 if (sCount < 4 && shadow > 0.02f) {
                     qo = (qo + qd * hT) + (qd * sBias) * 2.0f;
@@ -121,7 +127,15 @@
             sd = qd;
             sBias = fmaxf(0.002f, hT * 0.002f);
             sN = hitNormal<STRIDE>(S, C, hInst, hPrim, qd);
-            sMat = materialOf(S, R, hInst);
+            if constexpr (TEX) { // sample_material and the normal map, :273-316
+                sge_render_material sm;
+                F3 n = sN;
+                sampleSurface<STRIDE>(S, R, X, C, hInst, hPrim, uniformFloat(best.u), uniformFloat(best.v), qd, sm, n);
+                ps.sSurf = sm;
+                sN = n;
+            } else {
+                ps.sMat = materialOf(S, R, hInst);
+            }
             direct = F3{0, 0, 0};
             li = 0;
             pending = 0;
@@ -130,7 +144,7 @@
         }
 
         if (runLights) { // :322-376 (:473-524, :644-693)
-            const sge_render_material& m = R.materials[sMat];
+            const sge_render_material& m = surfaceS(ps, R);
             const F3 V = unit(-sd);
             const float camDist = length(sHit - cam);
             for (int k = 0; k <= nLights; ++k) {
@@ -160,11 +174,12 @@
         }
 
         if (surfaceDone) { // :378-380 (:525-530, :694-699)
-            const sge_render_material& m = R.materials[sMat];
+            const sge_render_material& m = surfaceS(ps, R);
             const F3 ambient = (mul(arr3(m.baseColor), evalEnvSH(sN, F)) * F.ambientIntensity) * m.occlusionStrength;
             const F3 color = (direct + ambient) + arr3(m.emissive);
             if (phase == 0) {
-                pHit = sHit; pN = sN; pd = sd; pBias = sBias; pMat = sMat; pColor = color;
+                pHit = sHit; pN = sN; pd = sd; pBias = sBias; pColor = color;
+                if constexpr (TEX) ps.pSurf = ps.sSurf; else ps.pMat = ps.sMat;
                 if (m.roughness <= 0.08f && m.metallic >= 0.8f) { // :383-390
                     if (layer == 0) aFlags |= 1;
                     qo = sHit + sN * sBias;
@@ -184,7 +199,7 @@
         }
 
         if (bounceDone) {
-            const sge_render_material& m = R.materials[pMat];
+            const sge_render_material& m = surfaceP(ps, R);
             const float NoV = sat(dot(pN, unit(-pd)));
             if (phase == 1) { // :537-541
                 const F3 reflColor = bAccum + bg * (1.0f - bAlpha);
@@ -203,7 +218,7 @@
         }
 
         if (checkRefraction) { // :545-561
-            const sge_render_material& m = R.materials[pMat];
+            const sge_render_material& m = surfaceP(ps, R);
             composite = true;
             if (m.transmission > 0.001f) {
                 const F3 V = unit(-pd);
@@ -228,7 +243,7 @@
         }
 
         if (composite) { // :715-721
-            const float alpha = R.materials[pMat].alpha;
+            const float alpha = surfaceP(ps, R).alpha;
             const float oneMinus = 1.0f - accumAlpha;
             accum = accum + (pColor * alpha) * oneMinus;
             accumAlpha += alpha * oneMinus;

@@ -36,6 +36,15 @@ __global__ __launch_bounds__(kWave) void scene_ragged_occlusion_kernel(SceneTrac
 template <int STRIDE>
 __global__ __launch_bounds__(kWave) void render_ragged_frame_kernel(const RenderArgs* A) {
     const RaggedCrowd<STRIDE> C{A->S.T, A->G};
+    constexpr bool TEX = STRIDE == 0; // false (a constant that depends on STRIDE: see the body)
+#include "sge_render_frame_body.inc"
+}
+
+// the textured form (include/sge_amd_render_textures.h; see sge_render.hip)
+template <int STRIDE>
+__global__ __launch_bounds__(kWave) void render_ragged_textured_kernel(const RenderArgs* A) {
+    const RaggedCrowd<STRIDE> C{A->S.T, A->G};
+    constexpr bool TEX = STRIDE != 0; // true
 #include "sge_render_frame_body.inc"
 }
 
@@ -56,6 +65,13 @@ void launch_render_frame_ragged(const RenderArgs& host, const RenderArgs* d_args
     if (n <= 0) return;
     if (host.S.T.layout == SGE_LAYOUT_PADDED16) hipLaunchKernelGGL((render_ragged_frame_kernel<4>), dim3(n), dim3(kWave), 0, s, d_args);
     else hipLaunchKernelGGL((render_ragged_frame_kernel<3>), dim3(n), dim3(kWave), 0, s, d_args);
+}
+
+void launch_render_frame_ragged_textured(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s) {
+    const int n = host.R.frame.width * host.R.frame.height;
+    if (n <= 0) return;
+    if (host.S.T.layout == SGE_LAYOUT_PADDED16) hipLaunchKernelGGL((render_ragged_textured_kernel<4>), dim3(n), dim3(kWave), 0, s, d_args);
+    else hipLaunchKernelGGL((render_ragged_textured_kernel<3>), dim3(n), dim3(kWave), 0, s, d_args);
 }
 
 } // namespace sge

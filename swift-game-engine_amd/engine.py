@@ -672,6 +672,47 @@ class CharacterEngine:
         f = np.ascontiguousarray(frame, abi.render_frame_dtype).reshape(1)
         self._call("render_frame_device", ptr(f), C.c_void_p(d_rgba), C.c_void_p(d_aov) if d_aov else None)
 
+    # -- textures in the shaded frame (include/sge_amd_render_textures.h; product only) -- #
+    def render_texture_upload(self, slot, rgba, srgb=False):
+        """texture.replace: rgba uint8 [height][width][4], row 0 first, as rgba8Unorm (or rgba8Unorm_srgb with srgb=True)."""
+        t = np.ascontiguousarray(rgba, np.uint8)
+        if t.ndim != 3 or t.shape[2] != 4:
+            raise SgeError("render_texture_upload: rgba must be [height][width][4] bytes")
+        self._call("render_texture_upload", int(slot), t.shape[1], t.shape[0], abi.TEX_RGBA8_UNORM_SRGB if srgb else abi.TEX_RGBA8_UNORM, ptr(t))
+
+    def render_texture_clear(self, slot=-1):
+        """Empties a slot (-1: all): a material that names it behaves as if it named no texture."""
+        self._call("render_texture_clear", int(slot))
+
+    def render_texture_info(self, slot):
+        """-> (width, height, format); (0, 0, 0) for an empty slot."""
+        w, h, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._call("render_texture_info_get", int(slot), C.byref(w), C.byref(h), C.byref(f))
+        return w.value, h.value, f.value
+
+    def render_material_textures(self, table):
+        """abi.render_material_textures_dtype records for materials [0, len(table)) (see abi.default_render_material_textures); every
+        other material returns to no textures."""
+        t = np.ascontiguousarray(table, abi.render_material_textures_dtype).reshape(-1)
+        self._call("render_material_textures_set", t.shape[0], ptr(t))
+
+    def render_srgb_table(self):
+        """The 256 float32 entries the kernels decode an rgba8Unorm_srgb colour channel with."""
+        t = np.zeros(256, np.float32)
+        self._call("render_srgb_table_get", ptr(t))
+        return t
+
+    def render_texture_sample(self, slot, uvs):
+        """The frame kernels' sampler alone -> float32 [n][4] at uvs [n][2]."""
+        u = np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+        out = np.zeros((u.shape[0], 4), np.float32)
+        self._call("render_texture_sample_batch", int(slot), ptr(u), u.shape[0], ptr(out))
+        return out
+
+    def render_texture_sample_device(self, slot, d_uvs, count, d_rgba):
+        """uvs / rgba already in device memory; asynchronous on the context's stream."""
+        self._call("render_texture_sample_device", int(slot), C.c_void_p(d_uvs), int(count), C.c_void_p(d_rgba))
+
     def blas_profile(self, reset=True):
         ms, n = C.c_double(0), C.c_int64(0)
         self._call("blas_profile_read", C.byref(ms), C.byref(n), int(reset))

@@ -28,6 +28,7 @@
 #include <vector>
 #include "../../include/sge_amd.h"
 #include "../../include/sge_amd_render.h"
+#include "../../include/sge_amd_render_textures.h"
 #include "../../include/sge_amd_variant_scene.h"
 
 namespace sge {
@@ -290,6 +291,32 @@ public:
     void setMaterials(const std::vector<sge_render_material>& m) { check(sge_render_materials_set(world_->context(), (int32_t)m.size(), m.data()), "sge_render_materials_set"); }
     void setStaticMaterials(const std::vector<int32_t>& m) { check(sge_render_static_materials(world_->context(), (int32_t)m.size(), m.data()), "sge_render_static_materials"); }
     void setCrowdMaterials(const std::vector<int32_t>& m) { check(sge_render_crowd_materials(world_->context(), (int32_t)m.size(), m.data()), "sge_render_crowd_materials"); }
+    // textures (include/sge_amd_render_textures.h): TextureResource's texture.replace into one of the 32 slots the kernel's texture
+    // array has (rgba8Unorm, or rgba8Unorm_srgb with srgb = true; rows tightly packed, row 0 first), and RTInstanceInfo's texture
+    // indices with normalScale, one entry per material (RTGeometryCache.swift:328-353)
+    void setTexture(int slot, int width, int height, bool srgb, const uint8_t* rgba) {
+        check(sge_render_texture_upload(world_->context(), slot, width, height, srgb ? SGE_TEX_RGBA8_UNORM_SRGB : SGE_TEX_RGBA8_UNORM, rgba), "sge_render_texture_upload");
+    }
+    void clearTexture(int slot = -1) { check(sge_render_texture_clear(world_->context(), slot), "sge_render_texture_clear"); }
+    void setMaterialTextures(const std::vector<sge_render_material_textures>& t) {
+        check(sge_render_material_textures_set(world_->context(), (int32_t)t.size(), t.data()), "sge_render_material_textures_set");
+    }
+    static sge_render_material_textures noTextures() { return sge_render_material_textures{-1, -1, -1, -1, -1, 1.0f, {0, 0}}; }
+    // width, height, format of a slot; all 0 when it is empty
+    void textureInfo(int slot, int32_t& width, int32_t& height, int32_t& format) const {
+        check(sge_render_texture_info_get(world_->context(), slot, &width, &height, &format), "sge_render_texture_info_get");
+    }
+    std::vector<float> srgbTable() const {
+        std::vector<float> t(256);
+        check(sge_render_srgb_table_get(world_->context(), t.data()), "sge_render_srgb_table_get");
+        return t;
+    }
+    // the frame kernels' sampler alone: rgba[count][4] at uvs[count][2]
+    std::vector<float> sampleTexture(int slot, const std::vector<float>& uvs) const {
+        std::vector<float> out(uvs.size() * 2);
+        check(sge_render_texture_sample_batch(world_->context(), slot, uvs.data(), (int32_t)(uvs.size() / 2), out.data()), "sge_render_texture_sample_batch");
+        return out;
+    }
     // whether the frame shows the crowd, through which table, and what is missing when it does not (include/sge_amd_variant_scene.h)
     sge_scene_crowd_status crowdStatus() const {
         sge_scene_crowd_status st{};

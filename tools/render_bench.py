@@ -8,7 +8,10 @@ same run and alternating with the frames: sge_scene_intersect_device on the fram
 With --variants, behind those lines and in the same process: the same frame, statics, materials and lights for the crowd with three
 mesh variants chosen by sge_lod_select from the camera (tools/variant_crowd.py) — first the control, whose variants all hold the full
 mesh (the ragged frame kernel over the uniform crowd's geometry), then full / half / quarter vertex count.
-usage: render_bench.py [--chars N] [--boxes K] [--width W] [--height H] [--frames F] [--variants] [--out FILE]"""
+With --textures, behind the first line and in the same process and context: the same frame with every material bound to a 256 x 256
+sRGB base-colour texture and the characters' materials also to a 256 x 256 normal map (include/sge_amd_render_textures.h; uvs on the
+statics are planar, the characters use the mesh's own), and the textured frame's median as a ratio to the untextured one.
+usage: render_bench.py [--chars N] [--boxes K] [--width W] [--height H] [--frames F] [--variants] [--textures] [--out FILE]"""
 import importlib, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,10 +40,10 @@ def flat_normals(pos, idx):
     return np.where(length > 0, nrm / np.maximum(length, 1e-30), (0.0, 1.0, 0.0)).astype(np.float32)
 
 
-def upload_mesh(eng, mesh, pos, idx):
+def upload_mesh(eng, mesh, pos, idx, uvs=None):
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
     idx = np.ascontiguousarray(idx, np.uint32).reshape(-1)
-    return eng.scene_mesh_upload(mesh, pos, flat_normals(pos, idx), np.tile(np.array([1, 0, 0, 1], np.float32), (len(pos), 1)), idx)
+    return eng.scene_mesh_upload(mesh, pos, flat_normals(pos, idx), np.tile(np.array([1, 0, 0, 1], np.float32), (len(pos), 1)), idx, uvs=uvs)
 
 
 eng = sge.CharacterEngine(0)
@@ -159,10 +162,17 @@ def measure(eng, label, uniform=None):
     return float(np.median(v))
 
 
-def dress(eng):
+def planar_uvs(pos, tiles=1):
+    """x / z over the mesh's extent in [0, 1], y mixed in so that walls vary too"""
+    span = np.maximum(np.ptp(pos, axis=0), 1e-6)
+    q = (pos - pos.min(0)) / span
+    return np.ascontiguousarray(np.stack([q[:, 0] * 0.8 + q[:, 1] * 0.2, q[:, 2] * 0.8 + q[:, 1] * 0.2], -1), np.float32)
+
+
+def dress(eng, uvs=False):
     """statics, materials and lights of the frame"""
-    upload_mesh(eng, 0, cpos, cheese["indices"])
-    upload_mesh(eng, 1, bp, bi)
+    upload_mesh(eng, 0, cpos, cheese["indices"], planar_uvs(cpos, 1) if uvs else None)
+    upload_mesh(eng, 1, bp, bi, planar_uvs(bp, 1) if uvs else None)
     eng.scene_instances(np.array([0] + [1] * boxes, np.int32), S.reshape(-1, 16))
     eng.render_materials(m)
     eng.render_static_materials(np.concatenate([[0], np.arange(boxes) % 3]).astype(np.int32))
@@ -171,6 +181,28 @@ def dress(eng):
 
 
 uniform_ms = measure(eng, "render_bench: %d x %d, %d characters + 17-Cheese (%d triangles) + %d boxes, opaque / mirror / glass materials, 2 lights" % (W, H, n, info.triangleCount, boxes))
+if "--textures" in sys.argv:
+    # the same context: uvs on every mesh, materials 3..5 = 0..2 for the characters (so that only they carry the normal map)
+    dress(eng, uvs=True)
+    eng.blas_set_uvs(eng.mesh["uvs"])
+    eng.render_materials(np.concatenate([m, m]))
+    eng.render_crowd_materials((3 + np.arange(n) % 3).astype(np.int32))
+    yy, xx = np.mgrid[0:256, 0:256]
+    base = np.full((256, 256, 4), 255, np.uint8)
+    cell = ((xx // 16 + yy // 16) % 2).astype(bool)
+    base[..., :3] = np.clip(np.where(cell[..., None], (230, 220, 200), (110, 120, 140)) + ((xx * 7 + yy * 13) % 11)[..., None] - 5, 0, 255)
+    nx, ny = 0.3 * np.cos(xx * np.pi / 16) * np.sin(yy * np.pi / 16), 0.3 * np.sin(xx * np.pi / 16) * np.cos(yy * np.pi / 16)
+    nn = np.stack([nx, ny, np.ones_like(nx)], -1)
+    nn /= np.linalg.norm(nn, axis=-1, keepdims=True)
+    bumps = np.full((256, 256, 4), 255, np.uint8)
+    bumps[..., :3] = np.rint((nn * 0.5 + 0.5) * 255)
+    eng.render_texture_upload(0, base, srgb=True)
+    eng.render_texture_upload(1, bumps, srgb=False)
+    bind = abi.default_render_material_textures(6)
+    bind["baseColor"] = 0
+    bind["normal"][3:] = 1
+    eng.render_material_textures(bind)
+    measure(eng, "(textures) the same frame, every material with a 256 x 256 sRGB base colour, the characters' also with a 256 x 256 normal map", uniform_ms)
 eng.close()
 if "--variants" in sys.argv:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
