@@ -191,7 +191,7 @@ def render_probe(engine, width=56, height=28, fov_y=0.6, scene=False):
     return h["hit"].reshape(height, width) == 1, h["distance"].reshape(height, width), h
 
 
-def shaded_image(engine, path, width=320, height=200, fov_y=0.9, textures=False):
+def shaded_image(engine, path, width=320, height=200, fov_y=0.9, textures=False, ibl=False):
     """The shaded frame (include/sge_amd_render.h: raytraceKernel's layers, lights and bounces in one launch) as a binary PPM, from a
     camera of its own that is pulled back until the mirror (a smooth metal: the mirror path), both platforms and the player are in
     view above the ground. -> the AOV records"""
@@ -223,6 +223,10 @@ def shaded_image(engine, path, width=320, height=200, fov_y=0.9, textures=False)
     mats["baseColor"][1], mats["metallic"][1], mats["roughness"][1] = (0.9, 0.9, 0.95), 1.0, 0.0
     mats["baseColor"][2], mats["roughness"][2] = (0.8, 0.45, 0.2), 0.6
     mats["baseColor"][3], mats["roughness"][3] = (0.3, 0.5, 0.9), 0.5
+    if ibl:   # include/sge_amd_render_ibl.h: IBLResources' default cube and table; the platforms become a rough metal that shows them
+        mats["metallic"][2], mats["roughness"][2] = 1.0, 0.4
+        engine.render_env_upload(128, 8, sge.ibl_default_env(128))
+        engine.render_brdf_lut_upload(sge.ibl_default_brdf_lut(128, 256))
     engine.render_materials(mats)
     engine.render_static_materials([0, 1] + [2] * (engine.scene_info().staticInstances - 2))
     engine.render_crowd_materials([3])
@@ -299,6 +303,7 @@ if __name__ == "__main__":
     ap.add_argument("--render", action="store_true", help="shoot primary rays and shadow rays at the whole scene (ground, mirror, platforms, player) after the last step and "
                     "print the depth image with shadowed pixels marked; with --oracle: primary rays at the characters only")
     ap.add_argument("--image", metavar="PATH", help="with --render (GPU library): also write the shaded frame of the scene (ground, mirror, platforms, shadowed player; a wider camera of its own) as a binary PPM")
+    ap.add_argument("--ibl", action="store_true", help="with --render --image: specular IBL from the reference's default environment cube and BRDF table; the platforms are a rough metal")
     ap.add_argument("--textures", action="store_true", help="with --render --image: a procedural checkerboard (sRGB) on the ground, a base-colour and a normal texture on the player")
     args = ap.parse_args()
     if args.oracle:
@@ -317,7 +322,7 @@ if __name__ == "__main__":
             mask.sum(), mask.size, (ids < A.SCENE_STATIC_BASE).sum(), (ids >= A.SCENE_STATIC_BASE).sum(), shadow.sum(), dist[mask].min(), dist[mask].max()))
         print(ascii_depth(mask, dist, shadow))
         if args.image:
-            aov = shaded_image(eng, args.image, textures=args.textures)
+            aov = shaded_image(eng, args.image, textures=args.textures, ibl=args.ibl)
             ids = aov["instance"]
             print("shaded frame %s: %d x %d, %d queries; pixels: %d ground, %d mirror (%d through the mirror path), %d platforms, %d player, %d with the sun shadowed" % (
                 args.image, aov.shape[1], aov.shape[0], aov["queries"].sum(), (ids == A.SCENE_STATIC_BASE).sum(), (ids == A.SCENE_STATIC_BASE + 1).sum(),

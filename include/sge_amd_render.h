@@ -13,8 +13,9 @@
  *     `...TexIndex < textureCount` test is false, so a material is its factors (:143-150) and the shading normal N is the
  *     geometric normal (:267-268). sge_amd_render_textures.h adds the texture slots, the per-material texture indices and the
  *     sampling sites of the text; while no material binds a slot that holds a texture, the frame is the one described here.
- *  2. No specular IBL. eval_spec_ibl (:88-104, :379) contributes 0; the environment cube, the BRDF table and a sampler that could
- *     be held to a reference are not part of this header.
+ *  2. No specular IBL in this header. On its own eval_spec_ibl (:88-104, :379) contributes 0. sge_amd_render_ibl.h adds the
+ *     environment cube, the BRDF table, their pinned samplers and the term; while either resource is missing, the frame is the
+ *     one described here.
  * Everything else is the text: maxLayers = 3 with the accumAlpha < 0.99 cut; shadow_bias; every enabled light, skipped when
  * camDist > maxDist or NdotL <= 0 (maxDistance <= 0 means 1e6); the shadow walk for light 0 only on the primary and mirror paths
  * but for every light on the refraction path (:654-689; the asymmetry is the reference's) — at most 4 occluders while shadow > 0.02,

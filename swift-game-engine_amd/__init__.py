@@ -8,4 +8,4 @@ fbx.py, exporters.py) and the reference-named C++ / Swift adapters (host/). The 
 importlib.import_module("swift-game-engine_amd").
 """
 from . import abi, assets, crowd, engine, exporters, fbx, formats, parallel, services  # noqa: F401
-from .engine import CharacterEngine, SgeError, make_queries  # noqa: F401
+from .engine import CharacterEngine, SgeError, ibl_default_brdf_lut, ibl_default_env, make_queries  # noqa: F401

@@ -483,6 +483,29 @@ RENDER_TEXTURE_PROTOTYPES = {
 }
 
 
+# include/sge_amd_render_ibl.h: specular IBL in the shaded frame (the environment cube in rgba16Float, the BRDF table, eval_spec_ibl).
+SGE_MAX_ENV_SIZE = 2048
+SGE_MAX_ENV_MIPS = 12
+SGE_MAX_BRDF_LUT_DIM = 4096
+RENDER_IBL_PROTOTYPES = {
+    "sge_render_env_upload": (C.c_int, [VP, i32, i32, VP]),
+    "sge_render_brdf_lut_upload": (C.c_int, [VP, i32, i32, VP]),
+    "sge_render_ibl_clear": (C.c_int, [VP]),
+    "sge_render_ibl_info_get": (C.c_int, [VP, P(i32), P(i32), P(i32), P(i32)]),
+    "sge_render_env_sample_batch": (C.c_int, [VP, VP, VP, i32, VP]),
+    "sge_render_brdf_lut_sample_batch": (C.c_int, [VP, VP, i32, VP]),
+    "sge_render_env_sample_device": (C.c_int, [VP, VP, VP, i32, VP]),
+    "sge_render_brdf_lut_sample_device": (C.c_int, [VP, VP, i32, VP]),
+    "sge_ibl_default_env_build": (C.c_int, [i32, i32, VP]),
+    "sge_ibl_default_brdf_lut_build": (C.c_int, [i32, i32, VP]),
+}
+
+
+def env_texel_count(size, mip_count):
+    """texels (of four halves) of a cube with `mip_count` levels: level m has six faces of max(size >> m, 1) squared"""
+    return sum(6 * max(size >> m, 1) ** 2 for m in range(mip_count))
+
+
 # include/sge_amd_variant_scene.h: a crowd with mesh variants in the ray scene and the shaded frame.
 class SceneCrowdStatus(C.Structure):
     _fields_ = [("crowdReady", i32), ("ragged", i32), ("reason", i32), ("variant", i32)]
@@ -537,7 +560,7 @@ def load_library(path=None):
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = bind(C.CDLL(path))
     for table in (VARIANT_PROTOTYPES, VARIANT_BLAS_PROTOTYPES, SCENE_PROTOTYPES, RENDER_PROTOTYPES, VARIANT_SCENE_PROTOTYPES,
-                  RENDER_TEXTURE_PROTOTYPES):
+                  RENDER_TEXTURE_PROTOTYPES, RENDER_IBL_PROTOTYPES):
         for name, (res, args) in table.items():  # (raises AttributeError if one is missing)
             fn = getattr(lib, name)
             fn.restype = res

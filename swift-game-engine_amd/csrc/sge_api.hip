@@ -188,6 +188,10 @@ struct sge_context {
     std::vector<sge_render_material_textures> hostMaterialTextures;
     bool renderTextured = false; // some bound slot holds a texture: the frame runs the textured kernels
     DevBuf dRenderTexTable, dRenderBindings, dRenderSrgb, dTexSampleUV, dTexSampleRGBA;
+    // specular IBL (include/sge_amd_render_ibl.h): the cube packed as halves, the table, the record the kernels read (renderIbl:
+    // device pointers and shapes; a null pointer is an empty resource) and its device copy for the sampler kernel
+    DevBuf dIblEnv, dIblLut, dIblRecord, dIblSampleIn, dIblSampleLod, dIblSampleOut;
+    RenderIBL renderIbl{};
     // stats / profiling
     DevBuf dStats, dWaveProf, dOrderHist, dSepAgents, dSepCounts, dSepFlow;
     int separationIterations = 2; float separationMargin = 0.2f, separationHeightMargin = 0.1f; // AgentSeparationSystem.init :2146-2152
@@ -885,6 +889,25 @@ int enqueueTextureSample(sge_context* c, int32_t slot, const float* d_uvs, int32
     return SGE_OK;
 }
 
+// ---- specular IBL (include/sge_amd_render_ibl.h) ----
+// the device copy of the record, behind every change of it; the caller has drained the device
+int uploadIblRecord(sge_context* c) {
+    int rc;
+    if ((rc = upload(c->dIblRecord, &c->renderIbl, sizeof(RenderIBL), c->stream)) != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    return SGE_OK;
+}
+int enqueueEnvSample(sge_context* c, const float* d_dirs, const float* d_lods, int32_t count, float* d_rgb) {
+    launch_env_sample(c->dIblRecord.as<RenderIBL>(), d_dirs, d_lods, count, d_rgb, c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+int enqueueLutSample(sge_context* c, const float* d_uvs, int32_t count, float* d_out) {
+    launch_brdf_lut_sample(c->dIblRecord.as<RenderIBL>(), d_uvs, count, d_out, c->stream);
+    SGE_HIP(hipGetLastError());
+    return SGE_OK;
+}
+
 // An assignment lives until the list it assigns is replaced: sge_scene_instances_set (another count, or another device list) and
 // sge_characters_resize (another count) are observed here, by every sge_render_* entry before it does anything else, and the
 // assignment is dropped for good: a later list of the old length starts from material 0 again.
@@ -930,13 +953,17 @@ int enqueueRenderFrame(sge_context* c, const sge_render_frame* f, float* d_rgba,
     A.R.rgba = d_rgba;
     A.R.aov = d_aov;
     const bool textured = c->renderTextured;
+    const bool ibl = c->renderIbl.env && c->renderIbl.lut; // specular IBL is active when both resources are present
+    if (ibl) A.I = c->renderIbl;
     if (textured) A.X = RenderTextures{c->dRenderTexTable.as<DevRenderTexture>(), c->dRenderBindings.as<sge_render_material_textures>(), c->dRenderSrgb.as<float>()};
     RenderArgs* d_args = c->dRenderArgs.as<RenderArgs>() + slot;
     SGE_HIP(hipMemcpyAsync(d_args, st.host, sizeof(RenderArgs), hipMemcpyHostToDevice, c->stream));
     SGE_HIP(hipEventRecord(st.copied, c->stream));
     st.inFlight = true;
     // the textured kernels only when a bound slot holds a texture: every other frame is the frame of sge_amd_render.h
-    if (ragged) (textured ? launch_render_frame_ragged_textured : launch_render_frame_ragged)(A, d_args, c->stream);
+    // and the IBL forms only when both the cube and the table are present
+    if (ibl) (ragged ? launch_render_frame_ragged_ibl : launch_render_frame_ibl)(A, d_args, textured, c->stream);
+    else if (ragged) (textured ? launch_render_frame_ragged_textured : launch_render_frame_ragged)(A, d_args, c->stream);
     else (textured ? launch_render_frame_textured : launch_render_frame)(A, d_args, c->stream);
     SGE_HIP(hipGetLastError());
     return SGE_OK;
@@ -1059,6 +1086,7 @@ void sge_context_destroy(sge_context* c) {
     for (DevBuf* b : {&c->dRenderMaterials, &c->dRenderStaticMaterial, &c->dRenderCrowdMaterial, &c->dRenderLights, &c->dRenderArgs, &c->dRenderRGBA, &c->dRenderAOV}) b->release();
     for (DevBuf* b : {&c->dRenderTexTable, &c->dRenderBindings, &c->dRenderSrgb, &c->dTexSampleUV, &c->dTexSampleRGBA}) b->release();
     for (auto& t : c->renderTextures) t.texels.release();
+    for (DevBuf* b : {&c->dIblEnv, &c->dIblLut, &c->dIblRecord, &c->dIblSampleIn, &c->dIblSampleLod, &c->dIblSampleOut}) b->release();
     for (DevBuf* b : {&c->dVariantTable, &c->dVariantOf, &c->dVariantSnap[0], &c->dVariantSnap[1], &c->dVertexOff, &c->dVariantLists, &c->dSkinPlan}) b->release();
     for (hipEvent_t e : {c->evVariantSnap, c->evPlanDone[0], c->evPlanDone[1], c->variantStage[0].copied, c->variantStage[1].copied}) if (e) (void)hipEventDestroy(e);
     for (auto& st : c->variantStage) if (st.host) (void)hipHostFree(st.host);
@@ -3001,6 +3029,114 @@ int sge_render_texture_sample_device(sge_context* c, int32_t slot, const void* d
     if (count == 0) return SGE_OK;
     (void)hipSetDevice(c->device);
     return enqueueTextureSample(c, slot, reinterpret_cast<const float*>(d_uvs), count, reinterpret_cast<float*>(d_rgba));
+}
+
+// ---- specular IBL in the shaded frame (include/sge_amd_render_ibl.h) ----
+int sge_render_env_upload(sge_context* c, int32_t size, int32_t mipCount, const uint16_t* texels) {
+    if (!c || !texels) { set_error("sge_render_env_upload: bad argument"); return SGE_ERR_INVALID; }
+    if (!envShapeOk(size, mipCount)) { set_error("sge_render_env_upload: size must be a power of two 1 .. SGE_MAX_ENV_SIZE and mipCount 1 .. log2(size) + 1"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    RenderIBL next = c->renderIbl;
+    size_t total = 0; // texels
+    for (int m = 0; m < SGE_MAX_ENV_MIPS; ++m) {
+        next.levelOff[m] = 0;
+        if (m >= mipCount) continue;
+        const size_t n = (size_t)std::max(size >> m, 1);
+        next.levelOff[m] = (uint32_t)total;
+        total += 6 * n * n;
+    }
+    // into a buffer of its own first: a failed allocation leaves the cube as it was
+    DevBuf fresh;
+    int rc = upload(fresh, texels, total * 8, c->stream);
+    if (rc == SGE_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("sge_render_env_upload: the copy failed"); rc = SGE_ERR_DEVICE; }
+    if (rc != SGE_OK) { fresh.release(); return rc; }
+    c->dIblEnv.release();
+    c->dIblEnv = fresh;
+    next.env = c->dIblEnv.as<uint16_t>();
+    next.size = size; next.mipCount = mipCount;
+    c->renderIbl = next;
+    return uploadIblRecord(c);
+}
+
+int sge_render_brdf_lut_upload(sge_context* c, int32_t width, int32_t height, const float* rgba) {
+    if (!c || !rgba) { set_error("sge_render_brdf_lut_upload: bad argument"); return SGE_ERR_INVALID; }
+    if (width < 1 || height < 1 || width > SGE_MAX_BRDF_LUT_DIM || height > SGE_MAX_BRDF_LUT_DIM) { set_error("sge_render_brdf_lut_upload: dimension outside 1 .. SGE_MAX_BRDF_LUT_DIM"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    DevBuf fresh;
+    int rc = upload(fresh, rgba, (size_t)width * height * 16, c->stream);
+    if (rc == SGE_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("sge_render_brdf_lut_upload: the copy failed"); rc = SGE_ERR_DEVICE; }
+    if (rc != SGE_OK) { fresh.release(); return rc; }
+    c->dIblLut.release();
+    c->dIblLut = fresh;
+    c->renderIbl.lut = c->dIblLut.as<float>();
+    c->renderIbl.lutW = width; c->renderIbl.lutH = height;
+    return uploadIblRecord(c);
+}
+
+int sge_render_ibl_clear(sge_context* c) {
+    if (!c) { set_error("sge_render_ibl_clear: bad argument"); return SGE_ERR_INVALID; }
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    c->dIblEnv.release();
+    c->dIblLut.release();
+    c->renderIbl = RenderIBL{};
+    return c->dIblRecord.p ? uploadIblRecord(c) : SGE_OK; // (the device copy names no freed buffer)
+}
+
+int sge_render_ibl_info_get(sge_context* c, int32_t* size, int32_t* mipCount, int32_t* lutWidth, int32_t* lutHeight) {
+    if (!c || !size || !mipCount || !lutWidth || !lutHeight) { set_error("sge_render_ibl_info_get: bad argument"); return SGE_ERR_INVALID; }
+    *size = c->renderIbl.size; *mipCount = c->renderIbl.mipCount;
+    *lutWidth = c->renderIbl.lutW; *lutHeight = c->renderIbl.lutH;
+    return SGE_OK;
+}
+
+int sge_render_env_sample_batch(sge_context* c, const float* dirs, const float* lods, int32_t count, float* rgb) {
+    if (!c || count < 0 || (count > 0 && (!dirs || !lods || !rgb))) { set_error("sge_render_env_sample_batch: bad argument"); return SGE_ERR_INVALID; }
+    if (!c->renderIbl.env) { set_error("sge_render_env_sample_batch: no environment cube is uploaded"); return SGE_ERR_STATE; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    int rc;
+    if ((rc = upload(c->dIblSampleIn, dirs, (size_t)count * 12, c->stream)) != SGE_OK) return rc;
+    if ((rc = upload(c->dIblSampleLod, lods, (size_t)count * 4, c->stream)) != SGE_OK) return rc;
+    if ((rc = c->dIblSampleOut.alloc((size_t)count * 12)) != SGE_OK) return rc;
+    if ((rc = enqueueEnvSample(c, c->dIblSampleIn.as<float>(), c->dIblSampleLod.as<float>(), count, c->dIblSampleOut.as<float>())) != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    SGE_HIP(hipMemcpy(rgb, c->dIblSampleOut.p, (size_t)count * 12, hipMemcpyDeviceToHost));
+    return SGE_OK;
+}
+
+int sge_render_brdf_lut_sample_batch(sge_context* c, const float* uvs, int32_t count, float* out) {
+    if (!c || count < 0 || (count > 0 && (!uvs || !out))) { set_error("sge_render_brdf_lut_sample_batch: bad argument"); return SGE_ERR_INVALID; }
+    if (!c->renderIbl.lut) { set_error("sge_render_brdf_lut_sample_batch: no BRDF table is uploaded"); return SGE_ERR_STATE; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    { int rcs = syncAll(c); if (rcs != SGE_OK) return rcs; }
+    int rc;
+    if ((rc = upload(c->dIblSampleIn, uvs, (size_t)count * 8, c->stream)) != SGE_OK) return rc;
+    if ((rc = c->dIblSampleOut.alloc((size_t)count * 8)) != SGE_OK) return rc;
+    if ((rc = enqueueLutSample(c, c->dIblSampleIn.as<float>(), count, c->dIblSampleOut.as<float>())) != SGE_OK) return rc;
+    SGE_HIP(hipStreamSynchronize(c->stream));
+    SGE_HIP(hipMemcpy(out, c->dIblSampleOut.p, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return SGE_OK;
+}
+
+int sge_render_env_sample_device(sge_context* c, const void* d_dirs, const void* d_lods, int32_t count, void* d_rgb) {
+    if (!c || count < 0 || (count > 0 && (!d_dirs || !d_lods || !d_rgb))) { set_error("sge_render_env_sample_device: bad argument"); return SGE_ERR_INVALID; }
+    if (!c->renderIbl.env) { set_error("sge_render_env_sample_device: no environment cube is uploaded"); return SGE_ERR_STATE; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    return enqueueEnvSample(c, reinterpret_cast<const float*>(d_dirs), reinterpret_cast<const float*>(d_lods), count, reinterpret_cast<float*>(d_rgb));
+}
+
+int sge_render_brdf_lut_sample_device(sge_context* c, const void* d_uvs, int32_t count, void* d_out) {
+    if (!c || count < 0 || (count > 0 && (!d_uvs || !d_out))) { set_error("sge_render_brdf_lut_sample_device: bad argument"); return SGE_ERR_INVALID; }
+    if (!c->renderIbl.lut) { set_error("sge_render_brdf_lut_sample_device: no BRDF table is uploaded"); return SGE_ERR_STATE; }
+    if (count == 0) return SGE_OK;
+    (void)hipSetDevice(c->device);
+    return enqueueLutSample(c, reinterpret_cast<const float*>(d_uvs), count, reinterpret_cast<float*>(d_out));
 }
 
 int sge_blas_profile_read(sge_context* c, double* ms, int64_t* launches, int reset) {

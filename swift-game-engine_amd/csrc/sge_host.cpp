@@ -636,4 +636,155 @@ int sge_blas_topology(const float* positions, int32_t vertex_count, const uint32
     return SGE_OK;
 }
 
+// ---- IBLResources.init (Game/IBLResources.swift), in float32 as written; include/sge_amd_render_ibl.h ----
+} // extern "C"
+
+namespace {
+
+using sge::F3;
+
+// Float16(x): round to nearest even
+uint16_t halfOf(float f) {
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (x > 0x7f800000u ? 0x200u : 0u)); // inf, NaN
+    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                                    // rounds to 65520 or more: inf
+    if (x < 0x38800000u) {                                                                      // below 2^-14: a denormal half
+        if (x < 0x33000000u) return (uint16_t)sign;                                             // below 2^-25: 0 (2^-25 itself ties to even: 0)
+        const int shift = 126 - (int)(x >> 23);                                                 // 14 .. 24
+        const uint32_t mant = (x & 0x7fffffu) | 0x800000u;
+        uint32_t h = mant >> shift;
+        const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
+        if (rem > half || (rem == half && (h & 1u))) ++h;
+        return (uint16_t)(sign | h);
+    }
+    uint32_t h = ((x - 0x38000000u) >> 13);
+    const uint32_t rem = x & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h; // (a carry into the exponent is the right result)
+    return (uint16_t)(sign | h);
+}
+
+F3 iblNormalize(F3 v) { return v / std::sqrt((v.x * v.x + v.y * v.y) + v.z * v.z); }
+float iblDot(F3 a, F3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+
+// :93-104
+F3 cubeDirection(int face, float u, float v) {
+    F3 d;
+    switch (face) {
+    case 0: d = F3{1.0f, -v, -u}; break;
+    case 1: d = F3{-1.0f, -v, u}; break;
+    case 2: d = F3{u, 1.0f, v}; break;
+    case 3: d = F3{u, -1.0f, -v}; break;
+    case 4: d = F3{u, -v, 1.0f}; break;
+    default: d = F3{-u, -v, -1.0f}; break;
+    }
+    return iblNormalize(d);
+}
+
+// :106-121
+F3 sampleEnvColor(F3 dir, float roughness) {
+    const F3 sky{0.65f, 0.72f, 0.9f}, ground{0.12f, 0.12f, 0.14f};
+    const float t = std::fmax(std::fmin(dir.y * 0.5f + 0.5f, 1.0f), 0.0f);
+    F3 color = ground + (sky - ground) * t;
+    const F3 sunDir = iblNormalize(F3{0.2f, 0.9f, 0.1f});
+    const float ndotl = std::fmax(iblDot(dir, sunDir), 0.0f);
+    const float exponent = 800.0f + (30.0f - 800.0f) * roughness;
+    const float sun = std::pow(ndotl, exponent) * 4.0f;
+    color = color + F3{sun, sun, sun};
+    auto clamp01 = [](float c) { return std::fmin(std::fmax(c, 0.0f), 1.0f); };
+    return F3{clamp01(color.x), clamp01(color.y), clamp01(color.z)};
+}
+
+// :150-158
+float radicalInverseVdC(uint32_t x) {
+    x = (x << 16) | (x >> 16);
+    x = ((x & 0x55555555u) << 1) | ((x & 0xAAAAAAAAu) >> 1);
+    x = ((x & 0x33333333u) << 2) | ((x & 0xCCCCCCCCu) >> 2);
+    x = ((x & 0x0F0F0F0Fu) << 4) | ((x & 0xF0F0F0F0u) >> 4);
+    x = ((x & 0x00FF00FFu) << 8) | ((x & 0xFF00FF00u) >> 8);
+    return (float)x * 2.3283064365386963e-10f;
+}
+
+// :160-167. Float.pi is the float32 below pi, 0x1.921fb4p+1.
+F3 importanceSampleGGX(float xix, float xiy, float roughness) {
+    const float a = roughness * roughness;
+    const float phi = (2.0f * 0x1.921fb4p+1f) * xix;
+    const float cosTheta = std::sqrt((1.0f - xiy) / (1.0f + (a * a - 1.0f) * xiy));
+    const float sinTheta = std::sqrt(std::fmax(1.0f - cosTheta * cosTheta, 0.0f));
+    return F3{std::cos(phi) * sinTheta, std::sin(phi) * sinTheta, cosTheta};
+}
+
+// :169-175
+float geometrySmith(float nDotV, float nDotL, float roughness) {
+    const float a = roughness;
+    const float k = (a * a) * 0.5f;
+    const float gV = nDotV / (nDotV * (1.0f - k) + k);
+    const float gL = nDotL / (nDotL * (1.0f - k) + k);
+    return gV * gL;
+}
+
+// :123-144
+void integrateBRDF(float nDotV, float roughness, int sampleCount, float out[2]) {
+    const F3 V{std::sqrt(std::fmax(1.0f - nDotV * nDotV, 0.0f)), 0.0f, nDotV};
+    float A = 0.0f, B = 0.0f;
+    for (int i = 0; i < sampleCount; ++i) {
+        const float xix = (float)i / (float)sampleCount, xiy = radicalInverseVdC((uint32_t)i);
+        const F3 H = importanceSampleGGX(xix, xiy, roughness);
+        const F3 L = iblNormalize(H * (2.0f * iblDot(V, H)) - V);
+        const float NoL = std::fmax(L.z, 0.0f);
+        const float NoH = std::fmax(H.z, 0.0f);
+        const float VoH = std::fmax(iblDot(V, H), 0.0f);
+        if (NoL > 0.0f) {
+            const float G = geometrySmith(nDotV, NoL, roughness);
+            const float GVis = (G * VoH) / std::fmax(NoH * nDotV, 1e-4f);
+            const float Fc = std::pow(1.0f - VoH, 5.0f);
+            A += (1.0f - Fc) * GVis;
+            B += Fc * GVis;
+        }
+    }
+    const float inv = 1.0f / (float)sampleCount;
+    out[0] = A * inv;
+    out[1] = B * inv;
+}
+
+
+} // namespace
+
+extern "C" {
+
+int sge_ibl_default_env_build(int32_t size, int32_t mipCount, uint16_t* texels) {
+    if (!texels || !sge::envShapeOk(size, mipCount)) { sge::set_error("sge_ibl_default_env_build: bad argument (size a power of two 1 .. SGE_MAX_ENV_SIZE, mipCount 1 .. log2(size) + 1)"); return SGE_ERR_INVALID; }
+    const uint16_t one = halfOf(1.0f);
+    uint16_t* o = texels;
+    for (int mip = 0; mip < mipCount; ++mip) {
+        const int n = std::max(size >> mip, 1);
+        const float roughness = mipCount > 1 ? (float)mip / (float)(mipCount - 1) : 0.0f;
+        for (int face = 0; face < 6; ++face)
+            for (int y = 0; y < n; ++y)
+                for (int x = 0; x < n; ++x, o += 4) {
+                    const float u = ((2.0f * ((float)x + 0.5f)) / (float)n) - 1.0f;
+                    const float v = ((2.0f * ((float)y + 0.5f)) / (float)n) - 1.0f;
+                    const F3 c = sampleEnvColor(cubeDirection(face, u, v), roughness);
+                    o[0] = halfOf(c.x); o[1] = halfOf(c.y); o[2] = halfOf(c.z); o[3] = one;
+                }
+    }
+    return SGE_OK;
+}
+
+int sge_ibl_default_brdf_lut_build(int32_t size, int32_t sampleCount, float* rgba) {
+    if (!rgba || size < 1 || size > SGE_MAX_BRDF_LUT_DIM || sampleCount < 1 || sampleCount > 65536) { sge::set_error("sge_ibl_default_brdf_lut_build: bad argument (size 1 .. SGE_MAX_BRDF_LUT_DIM, sampleCount 1 .. 65536)"); return SGE_ERR_INVALID; }
+    for (int y = 0; y < size; ++y) {
+        const float roughness = std::fmax((float)y / (float)(size - 1), 0.001f);
+        for (int x = 0; x < size; ++x) {
+            const float nDotV = std::fmax((float)x / (float)(size - 1), 0.001f);
+            float* o = rgba + ((size_t)y * size + x) * 4;
+            integrateBRDF(nDotV, roughness, sampleCount, o);
+            o[2] = 0.0f; o[3] = 0.0f;
+        }
+    }
+    return SGE_OK;
+}
+
 } // extern "C"

@@ -10,6 +10,7 @@
 #include "../../include/sge_amd_ray_scene.h"
 #include "../../include/sge_amd_render.h"
 #include "../../include/sge_amd_render_textures.h"
+#include "../../include/sge_amd_render_ibl.h"
 #include "../../include/sge_amd_variant_scene.h"
 #include "sge_math.hpp"
 
@@ -522,13 +523,36 @@ struct RenderTextures {
                                                   // holds a texture, or -1
     const float* srgb;                            // device [256]: the decode table of the header
 };
-// (X: behind the records the untextured kernels read; filled and read only when a bound slot holds a texture)
-struct RenderArgs { SceneTrace S; RenderLaunch R; SceneRagged G; RenderTextures X; };
+// Specular IBL (include/sge_amd_render_ibl.h). The cube stays packed as halves, rgba, level-major then face then row; levelOff[m]:
+// where level m starts, in texels. The table: float rgba texels, row 0 first. env null / lut null: empty.
+struct RenderIBL {
+    const uint16_t* env;
+    const float* lut;
+    int size, mipCount, lutW, lutH;
+    uint32_t levelOff[SGE_MAX_ENV_MIPS];
+};
+// sge_render_env_upload's and sge_ibl_default_env_build's shape rule: size a power of two 1 .. SGE_MAX_ENV_SIZE, mipCount 1 .. log2(size) + 1
+inline bool envShapeOk(int32_t size, int32_t mipCount) {
+    if (size < 1 || size > SGE_MAX_ENV_SIZE || (size & (size - 1)) != 0) return false;
+    int levels = 1;
+    for (int s = size; s > 1; s >>= 1) ++levels;
+    return mipCount >= 1 && mipCount <= levels;
+}
+// (X: behind the records the untextured kernels read; filled and read only when a bound slot holds a texture. I: behind X; filled
+// and read only when both the cube and the table are present)
+struct RenderArgs { SceneTrace S; RenderLaunch R; SceneRagged G; RenderTextures X; RenderIBL I; };
 void launch_render_frame(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
 void launch_render_frame_ragged(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
 // the textured forms of the two (render_textured_kernel, render_ragged_textured_kernel)
 void launch_render_frame_textured(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
 void launch_render_frame_ragged_textured(const RenderArgs& host, const RenderArgs* d_args, hipStream_t s);
+// the forms with specular IBL (render_ibl_kernel, render_ibl_tex_kernel, render_ragged_ibl_kernel, render_ragged_ibl_tex_kernel)
+void launch_render_frame_ibl(const RenderArgs& host, const RenderArgs* d_args, bool textured, hipStream_t s);
+void launch_render_frame_ragged_ibl(const RenderArgs& host, const RenderArgs* d_args, bool textured, hipStream_t s);
+// the IBL samplers alone (ibl_sample_kernel): rgb[n][3] = the cube at dirs[n][3], lods[n]; out[n][2] = the table at uvs[n][2]
+// (d_ibl: a device copy of the record)
+void launch_env_sample(const RenderIBL* d_ibl, const float* d_dirs, const float* d_lods, int n, float* d_rgb, hipStream_t s);
+void launch_brdf_lut_sample(const RenderIBL* d_ibl, const float* d_uvs, int n, float* d_out, hipStream_t s);
 // the sampler alone: rgba[n][4] = tex at uvs[n][2] (device arrays), one thread per sample
 void launch_texture_sample(const DevRenderTexture& tex, const float* srgb, const float* d_uvs, int n, float* d_rgba, hipStream_t s);
 

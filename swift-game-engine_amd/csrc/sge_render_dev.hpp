@@ -128,6 +128,100 @@ __device__ __forceinline__ void texSample(const DevRenderTexture& t, const float
     }
 }
 
+// ---- specular IBL (include/sge_amd_render_ibl.h) ----
+
+// the face selection of the header and the inverse of cubeDirection (IBLResources.swift:93-104)
+struct CubeCoord { int face; float u, v; };
+__device__ __forceinline__ CubeCoord cubeCoordOf(F3 d) {
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    if (ax >= ay && ax >= az) return d.x < 0.0f ? CubeCoord{1, d.z / ax, -d.y / ax} : CubeCoord{0, -d.z / ax, -d.y / ax};
+    if (ay >= az) return d.y < 0.0f ? CubeCoord{3, d.x / ay, -d.z / ay} : CubeCoord{2, d.x / ay, d.z / ay};
+    return d.z < 0.0f ? CubeCoord{5, -d.x / az, -d.y / az} : CubeCoord{4, d.x / az, -d.y / az};
+}
+// cubeDirection, not normalised
+__device__ __forceinline__ F3 cubeDirectionOf(int face, float u, float v) {
+    switch (face) {
+    case 0: return F3{1.0f, -v, -u};
+    case 1: return F3{-1.0f, -v, u};
+    case 2: return F3{u, 1.0f, v};
+    case 3: return F3{u, -1.0f, -v};
+    case 4: return F3{u, -v, 1.0f};
+    default: return F3{-u, -v, -1.0f};
+    }
+}
+// One tap of a level whose faces are n x n: (i, j) in -1 .. n; a tap outside the face reads the texel that holds the direction of
+// its centre. Every index that reaches the load is inside 0 .. n - 1 and face inside 0 .. 5, whatever the inputs were.
+__device__ __forceinline__ F3 cubeTap(const uint16_t* level, int n, int face, int i, int j) {
+    if (i < 0 || i >= n || j < 0 || j >= n) {
+        const float uc = (2.0f * ((float)i + 0.5f)) / (float)n - 1.0f;
+        const float vc = (2.0f * ((float)j + 0.5f)) / (float)n - 1.0f;
+        const CubeCoord c = cubeCoordOf(cubeDirectionOf(face, uc, vc));
+        face = c.face;
+        i = min(max((int)floorf(((c.u + 1.0f) * 0.5f) * (float)n), 0), n - 1);
+        j = min(max((int)floorf(((c.v + 1.0f) * 0.5f) * (float)n), 0), n - 1);
+    }
+    const uint2 w = *reinterpret_cast<const uint2*>(level + (((size_t)face * n + j) * n + i) * 4);
+    const _Float16 r = __builtin_bit_cast(_Float16, (uint16_t)(w.x & 0xffffu));
+    const _Float16 g = __builtin_bit_cast(_Float16, (uint16_t)(w.x >> 16));
+    const _Float16 b = __builtin_bit_cast(_Float16, (uint16_t)(w.y & 0xffffu));
+    return F3{(float)r, (float)g, (float)b};
+}
+__device__ __forceinline__ F3 cubeLevelSample(const RenderIBL& I, int l, const CubeCoord& c) {
+    const int n = max(I.size >> l, 1);
+    const uint16_t* level = I.env + (size_t)I.levelOff[l] * 4;
+    const float x = fminf(fmaxf(((c.u + 1.0f) * 0.5f) * (float)n - 0.5f, -0.5f), (float)n - 0.5f);
+    const float y = fminf(fmaxf(((c.v + 1.0f) * 0.5f) * (float)n - 0.5f, -0.5f), (float)n - 0.5f);
+    const int x0 = (int)floorf(x), y0 = (int)floorf(y);
+    const int x1 = x0 + 1, y1 = y0 + 1;
+    const float fx = x - (float)x0, fy = y - (float)y0;
+    const F3 t00 = cubeTap(level, n, c.face, x0, y0), t10 = cubeTap(level, n, c.face, x1, y0);
+    const F3 t01 = cubeTap(level, n, c.face, x0, y1), t11 = cubeTap(level, n, c.face, x1, y1);
+    const F3 top = t00 * (1.0f - fx) + t10 * fx;
+    const F3 bot = t01 * (1.0f - fx) + t11 * fx;
+    return top * (1.0f - fy) + bot * fy;
+}
+// envMap.sample(samp, d, level(lod)).xyz
+__device__ __forceinline__ F3 envSample(const RenderIBL& I, F3 d, float lod) {
+    const float mip = fminf(fmaxf(lod, 0.0f), (float)(I.mipCount - 1));
+    const int l0 = (int)floorf(mip);
+    const int l1 = min(l0 + 1, I.mipCount - 1);
+    const float fl = mip - (float)l0;
+    const CubeCoord c = cubeCoordOf(d);
+    const F3 c0 = cubeLevelSample(I, l0, c), c1 = cubeLevelSample(I, l1, c);
+    return c0 * (1.0f - fl) + c1 * fl;
+}
+// brdfLUT.sample(samp, (u, v)).xy: texSample's coordinates and filter over float texels
+__device__ __forceinline__ void brdfLutSample(const RenderIBL& I, float u, float v, float out[2]) {
+    const int W = I.lutW, H = I.lutH;
+    const float x = fminf(fmaxf(u * (float)W - 0.5f, 0.0f), (float)(W - 1));
+    const float y = fminf(fmaxf(v * (float)H - 0.5f, 0.0f), (float)(H - 1));
+    const int x0 = (int)floorf(x), y0 = (int)floorf(y);
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    const float fx = x - (float)x0, fy = y - (float)y0;
+    const float2* r0 = reinterpret_cast<const float2*>(I.lut + (size_t)y0 * W * 4);
+    const float2* r1 = reinterpret_cast<const float2*>(I.lut + (size_t)y1 * W * 4);
+    const float2 t00 = r0[x0 * 2], t10 = r0[x1 * 2], t01 = r1[x0 * 2], t11 = r1[x1 * 2];
+    const float topx = t00.x * (1.0f - fx) + t10.x * fx, botx = t01.x * (1.0f - fx) + t11.x * fx;
+    const float topy = t00.y * (1.0f - fx) + t10.y * fx, boty = t01.y * (1.0f - fx) + t11.y * fx;
+    out[0] = topx * (1.0f - fy) + botx * fy;
+    out[1] = topy * (1.0f - fy) + boty * fy;
+}
+// eval_spec_ibl (RayTracing.metalinc:88-104). In the frame kernels every lane holds the same N, V and surface: R, the level and
+// the table's coordinate are made scalar, so every tap is a wave-uniform load.
+__device__ __forceinline__ F3 evalSpecIbl(const RenderIBL& I, F3 N, F3 V, float roughness, float metallic, F3 base) {
+    const float NoV = uniformFloat(sat(dot(N, V)));
+    const F3 In = -V;
+    const F3 Rr = In - N * (2.0f * dot(N, In));
+    const F3 Rd{uniformFloat(Rr.x), uniformFloat(Rr.y), uniformFloat(Rr.z)};
+    const float rough = uniformFloat(roughness);
+    const float mip = rough * fmaxf((float)(I.mipCount - 1), 0.0f);
+    const F3 prefiltered = envSample(I, Rd, mip);
+    float brdf[2];
+    brdfLutSample(I, NoV, rough, brdf);
+    const F3 F0 = F3{0.04f, 0.04f, 0.04f} + (base - F3{0.04f, 0.04f, 0.04f}) * metallic;
+    return mul(prefiltered, F0 * brdf[0] + F3{brdf[1], brdf[1], brdf[1]});
+}
+
 // The hit record of sge_scene_intersect_* at a hit the scan reported: blasHitRecord over whichever half's streams hold the
 // triangle, as the tail of sge_scene_trace_body.inc calls it. (u, v) are the barycentrics the walk left.
 template <int STRIDE, class Crowd>

@@ -4,7 +4,8 @@
 // crowd half's accessor over A->S.T (sge_ray_scene_dev.hpp), and TEX, a constant that depends on STRIDE (so that the arm of an
 // `if constexpr (TEX)` that is not taken is discarded unseen): true in the textured kernels (include/sge_amd_render_textures.h),
 // which sample where the text samples and carry the sampled surface; false in the kernels of sge_amd_render.h, which compile to
-// what they were.
+// what they were. IBL, a constant of the same kind: true in the kernels of include/sge_amd_render_ibl.h, which add eval_spec_ibl
+// to the colour of the layer's own surface.
     __shared__ int stack[kBlasStack];
     const int lane = threadIdx.x;
     // (the two records are read where they are used, from device memory: as kernel arguments they were held in scalar registers
@@ -14,6 +15,7 @@
     const sge_render_frame& F = R.frame;
     const BlasTrace& T = S.T;
     const RenderTextures& X = A->X; // (read by the textured form only)
+    const RenderIBL& E = A->I;      // (read by the IBL forms only)
     const int W = F.width, H = F.height;
     const int pixel = blockIdx.x;
     if (pixel >= W * H) return;
@@ -176,7 +178,14 @@
         if (surfaceDone) { // :378-380 (:525-530, :694-699)
             const sge_render_material& m = surfaceS(ps, R);
             const F3 ambient = (mul(arr3(m.baseColor), evalEnvSH(sN, F)) * F.ambientIntensity) * m.occlusionStrength;
-            const F3 color = (direct + ambient) + arr3(m.emissive);
+            F3 color;
+            if constexpr (IBL) { // :379-380: eval_spec_ibl, at the layer's own surface only
+                F3 lit = direct + ambient;
+                if (phase == 0) lit = lit + evalSpecIbl(E, sN, unit(-sd), m.roughness, m.metallic, arr3(m.baseColor)) * m.occlusionStrength;
+                color = lit + arr3(m.emissive);
+            } else {
+                color = (direct + ambient) + arr3(m.emissive);
+            }
             if (phase == 0) {
                 pHit = sHit; pN = sN; pd = sd; pBias = sBias; pColor = color;
                 if constexpr (TEX) ps.pSurf = ps.sSurf; else ps.pMat = ps.sMat;

@@ -37,6 +37,7 @@ template <int STRIDE>
 __global__ __launch_bounds__(kWave) void render_ragged_frame_kernel(const RenderArgs* A) {
     const RaggedCrowd<STRIDE> C{A->S.T, A->G};
     constexpr bool TEX = STRIDE == 0; // false (a constant that depends on STRIDE: see the body)
+    constexpr bool IBL = STRIDE == 0; // false
 #include "sge_render_frame_body.inc"
 }
 
@@ -45,6 +46,24 @@ template <int STRIDE>
 __global__ __launch_bounds__(kWave) void render_ragged_textured_kernel(const RenderArgs* A) {
     const RaggedCrowd<STRIDE> C{A->S.T, A->G};
     constexpr bool TEX = STRIDE != 0; // true
+    constexpr bool IBL = STRIDE == 0; // false
+#include "sge_render_frame_body.inc"
+}
+
+// the forms with specular IBL (include/sge_amd_render_ibl.h; see sge_render.hip)
+template <int STRIDE>
+__global__ __launch_bounds__(kWave) void render_ragged_ibl_kernel(const RenderArgs* A) {
+    const RaggedCrowd<STRIDE> C{A->S.T, A->G};
+    constexpr bool TEX = STRIDE == 0; // false
+    constexpr bool IBL = STRIDE != 0; // true
+#include "sge_render_frame_body.inc"
+}
+
+template <int STRIDE>
+__global__ __launch_bounds__(kWave) void render_ragged_ibl_tex_kernel(const RenderArgs* A) {
+    const RaggedCrowd<STRIDE> C{A->S.T, A->G};
+    constexpr bool TEX = STRIDE != 0; // true
+    constexpr bool IBL = STRIDE != 0; // true
 #include "sge_render_frame_body.inc"
 }
 
@@ -72,6 +91,19 @@ void launch_render_frame_ragged_textured(const RenderArgs& host, const RenderArg
     if (n <= 0) return;
     if (host.S.T.layout == SGE_LAYOUT_PADDED16) hipLaunchKernelGGL((render_ragged_textured_kernel<4>), dim3(n), dim3(kWave), 0, s, d_args);
     else hipLaunchKernelGGL((render_ragged_textured_kernel<3>), dim3(n), dim3(kWave), 0, s, d_args);
+}
+
+void launch_render_frame_ragged_ibl(const RenderArgs& host, const RenderArgs* d_args, bool textured, hipStream_t s) {
+    const int n = host.R.frame.width * host.R.frame.height;
+    if (n <= 0) return;
+    const bool padded = host.S.T.layout == SGE_LAYOUT_PADDED16;
+    if (textured) {
+        if (padded) hipLaunchKernelGGL((render_ragged_ibl_tex_kernel<4>), dim3(n), dim3(kWave), 0, s, d_args);
+        else hipLaunchKernelGGL((render_ragged_ibl_tex_kernel<3>), dim3(n), dim3(kWave), 0, s, d_args);
+    } else {
+        if (padded) hipLaunchKernelGGL((render_ragged_ibl_kernel<4>), dim3(n), dim3(kWave), 0, s, d_args);
+        else hipLaunchKernelGGL((render_ragged_ibl_kernel<3>), dim3(n), dim3(kWave), 0, s, d_args);
+    }
 }
 
 } // namespace sge

@@ -713,6 +713,57 @@ class CharacterEngine:
         """uvs / rgba already in device memory; asynchronous on the context's stream."""
         self._call("render_texture_sample_device", int(slot), C.c_void_p(d_uvs), int(count), C.c_void_p(d_rgba))
 
+    # -- specular IBL in the shaded frame (include/sge_amd_render_ibl.h; product only) -- #
+    def render_env_upload(self, size, mip_count, texels):
+        """The environment cube in rgba16Float: float16 (or its uint16 bits) [texels][4], level-major, then face +X -X +Y -Y +Z -Z,
+        then rows (abi.env_texel_count(size, mip_count) texels)."""
+        t = np.asarray(texels)
+        t = np.ascontiguousarray(t.view(np.uint16) if t.dtype == np.float16 else t, np.uint16).reshape(-1)
+        if size >= 1 and 1 <= mip_count <= abi.SGE_MAX_ENV_MIPS and t.shape[0] != 4 * abi.env_texel_count(size, mip_count):
+            raise SgeError("render_env_upload: texels must hold %d halves" % (4 * abi.env_texel_count(size, mip_count)))
+        self._call("render_env_upload", int(size), int(mip_count), ptr(t))
+
+    def render_brdf_lut_upload(self, rgba):
+        """The BRDF table in rgba32Float: float32 [height][width][4]; the kernels read x and y."""
+        t = np.ascontiguousarray(rgba, np.float32)
+        if t.ndim != 3 or t.shape[2] != 4:
+            raise SgeError("render_brdf_lut_upload: rgba must be [height][width][4] floats")
+        self._call("render_brdf_lut_upload", t.shape[1], t.shape[0], ptr(t))
+
+    def render_ibl_clear(self):
+        """Empties the cube and the table: eval_spec_ibl contributes 0 again."""
+        self._call("render_ibl_clear")
+
+    def render_ibl_info(self):
+        """-> (size, mipCount, lutWidth, lutHeight); zeros for an empty resource."""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._call("render_ibl_info_get", *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def render_env_sample(self, dirs, lods):
+        """The frame kernels' cube sampler alone -> float32 [n][3] at directions [n][3] and levels of detail [n]."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        l = np.ascontiguousarray(lods, np.float32).reshape(-1)
+        if l.shape[0] != d.shape[0]:
+            raise SgeError("render_env_sample: one lod per direction")
+        out = np.zeros((d.shape[0], 3), np.float32)
+        self._call("render_env_sample_batch", ptr(d), ptr(l), d.shape[0], ptr(out))
+        return out
+
+    def render_brdf_lut_sample(self, uvs):
+        """The frame kernels' table sampler alone -> float32 [n][2] (x and y) at uvs [n][2]."""
+        u = np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+        out = np.zeros((u.shape[0], 2), np.float32)
+        self._call("render_brdf_lut_sample_batch", ptr(u), u.shape[0], ptr(out))
+        return out
+
+    def render_env_sample_device(self, d_dirs, d_lods, count, d_rgb):
+        """dirs / lods / rgb already in device memory; asynchronous on the context's stream."""
+        self._call("render_env_sample_device", C.c_void_p(d_dirs), C.c_void_p(d_lods), int(count), C.c_void_p(d_rgb))
+
+    def render_brdf_lut_sample_device(self, d_uvs, count, d_out):
+        self._call("render_brdf_lut_sample_device", C.c_void_p(d_uvs), int(count), C.c_void_p(d_out))
+
     def blas_profile(self, reset=True):
         ms, n = C.c_double(0), C.c_int64(0)
         self._call("blas_profile_read", C.byref(ms), C.byref(n), int(reset))
@@ -787,6 +838,30 @@ class CharacterEngine:
         st = abi.MoveStats()
         self._call("move_stats_read", C.byref(st), int(reset))
         return st
+
+
+def _host_call(name, *args):
+    lib = abi.load_library()
+    rc = getattr(lib, name)(*args)
+    if rc != abi.SGE_OK:
+        raise SgeError(f"{name} failed with code {rc}: {(lib.sge_last_error() or b'').decode()}")
+
+
+def ibl_default_env(size=128, mip_count=None):
+    """IBLResources.init's cube (include/sge_amd_render_ibl.h), built on the host -> float16 [texels][4] as render_env_upload takes
+    it. mip_count None: the full chain, as `mipmapped: true` gives."""
+    if mip_count is None:
+        mip_count = max(int(size), 1).bit_length()
+    out = np.zeros((abi.env_texel_count(size, mip_count) if 1 <= mip_count <= abi.SGE_MAX_ENV_MIPS and size >= 1 else 1, 4), np.uint16)
+    _host_call("sge_ibl_default_env_build", int(size), int(mip_count), ptr(out))
+    return out.view(np.float16)
+
+
+def ibl_default_brdf_lut(size=128, sample_count=256):
+    """IBLResources.init's BRDF table, built on the host -> float32 [size][size][4] as render_brdf_lut_upload takes it."""
+    out = np.zeros((max(int(size), 1), max(int(size), 1), 4), np.float32)
+    _host_call("sge_ibl_default_brdf_lut_build", int(size), int(sample_count), ptr(out))
+    return out
 
 
 def make_queries(origins, deltas=None, radius=1.5, half_height=1.0, mode=abi.CAST, min_normal_y=0.5, mask=0xFFFFFFFF):

@@ -29,6 +29,7 @@
 #include "../../include/sge_amd.h"
 #include "../../include/sge_amd_render.h"
 #include "../../include/sge_amd_render_textures.h"
+#include "../../include/sge_amd_render_ibl.h"
 #include "../../include/sge_amd_variant_scene.h"
 
 namespace sge {
@@ -285,6 +286,31 @@ struct DirectionalLight {   // Components.swift DirectionalLight as updateLightB
     float maxDistance = 200.0f;
 };
 
+// IBLResources (Game/IBLResources.swift; include/sge_amd_render_ibl.h): the environment cube in rgba16Float (halves, level-major, then
+// face +X -X +Y -Y +Z -Z, then rows) and the BRDF table in rgba32Float, held on the host; RayTracingRenderer::setIBL uploads them.
+// The default constructor is IBLResources.init: the procedural cube at 128 with its full mip chain and the 128 x 128 table
+// integrated with 256 samples, both built on the host in float32 as the text writes them.
+class IBLResources {
+public:
+    std::vector<uint16_t> envCube;
+    std::vector<float> brdfLUT;
+    int32_t envSize = 0;
+    uint32_t envMipCount = 0;
+    int32_t lutSize = 0;
+    IBLResources() : IBLResources(128, 128, 256) {}
+    IBLResources(int32_t cubeSize, int32_t tableSize, int32_t sampleCount) : envSize(cubeSize), lutSize(tableSize) {
+        int32_t mips = 1;
+        for (int32_t s = cubeSize; s > 1; s >>= 1) ++mips;
+        size_t texels = 0;
+        for (int32_t m = 0; m < mips; ++m) { const size_t n = (size_t)((cubeSize >> m) > 1 ? (cubeSize >> m) : 1); texels += 6 * n * n; }
+        envCube.assign(cubeSize >= 1 ? texels * 4 : 4, 0);
+        check(sge_ibl_default_env_build(cubeSize, mips, envCube.data()), "sge_ibl_default_env_build");
+        envMipCount = (uint32_t)mips;
+        brdfLUT.assign(tableSize >= 1 ? (size_t)tableSize * tableSize * 4 : 4, 0.0f);
+        check(sge_ibl_default_brdf_lut_build(tableSize, sampleCount, brdfLUT.data()), "sge_ibl_default_brdf_lut_build");
+    }
+};
+
 class RayTracingRenderer {
 public:
     explicit RayTracingRenderer(World& w) : world_(&w) {}
@@ -315,6 +341,28 @@ public:
     std::vector<float> sampleTexture(int slot, const std::vector<float>& uvs) const {
         std::vector<float> out(uvs.size() * 2);
         check(sge_render_texture_sample_batch(world_->context(), slot, uvs.data(), (int32_t)(uvs.size() / 2), out.data()), "sge_render_texture_sample_batch");
+        return out;
+    }
+    // specular IBL (include/sge_amd_render_ibl.h): the envMap and brdfLUT bindings of RayTracingRenderer.swift:141 and
+    // frame.envMipCount of :86. The term is active while both are set; clearIBL returns to the frame without it.
+    void setIBL(const IBLResources& ibl) {
+        check(sge_render_env_upload(world_->context(), ibl.envSize, (int32_t)ibl.envMipCount, ibl.envCube.data()), "sge_render_env_upload");
+        check(sge_render_brdf_lut_upload(world_->context(), ibl.lutSize, ibl.lutSize, ibl.brdfLUT.data()), "sge_render_brdf_lut_upload");
+    }
+    void clearIBL() { check(sge_render_ibl_clear(world_->context()), "sge_render_ibl_clear"); }
+    // size and mipCount of the cube, width and height of the table; zeros for an empty resource
+    void iblInfo(int32_t& size, int32_t& mipCount, int32_t& lutWidth, int32_t& lutHeight) const {
+        check(sge_render_ibl_info_get(world_->context(), &size, &mipCount, &lutWidth, &lutHeight), "sge_render_ibl_info_get");
+    }
+    // the frame kernels' samplers alone: rgb[count][3] at dirs[count][3] and lods[count]; xy[count][2] at uvs[count][2]
+    std::vector<float> sampleEnvironment(const std::vector<float>& dirs, const std::vector<float>& lods) const {
+        std::vector<float> out(lods.size() * 3);
+        check(sge_render_env_sample_batch(world_->context(), dirs.data(), lods.data(), (int32_t)lods.size(), out.data()), "sge_render_env_sample_batch");
+        return out;
+    }
+    std::vector<float> sampleBrdfLUT(const std::vector<float>& uvs) const {
+        std::vector<float> out(uvs.size());
+        check(sge_render_brdf_lut_sample_batch(world_->context(), uvs.data(), (int32_t)(uvs.size() / 2), out.data()), "sge_render_brdf_lut_sample_batch");
         return out;
     }
     // whether the frame shows the crowd, through which table, and what is missing when it does not (include/sge_amd_variant_scene.h)

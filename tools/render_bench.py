@@ -11,7 +11,10 @@ mesh (the ragged frame kernel over the uniform crowd's geometry), then full / ha
 With --textures, behind the first line and in the same process and context: the same frame with every material bound to a 256 x 256
 sRGB base-colour texture and the characters' materials also to a 256 x 256 normal map (include/sge_amd_render_textures.h; uvs on the
 statics are planar, the characters use the mesh's own), and the textured frame's median as a ratio to the untextured one.
-usage: render_bench.py [--chars N] [--boxes K] [--width W] [--height H] [--frames F] [--variants] [--textures] [--out FILE]"""
+With --ibl, behind those lines in the same process and context: the same frame(s) with the reference's default environment (the
+128 cube with its 8 levels, the 128 x 128 BRDF table; include/sge_amd_render_ibl.h) — the untextured frame with the term, and with
+--textures also the textured frame with the term — each as a ratio to its own line without the term.
+usage: render_bench.py [--chars N] [--boxes K] [--width W] [--height H] [--frames F] [--variants] [--textures] [--ibl] [--out FILE]"""
 import importlib, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -180,7 +183,18 @@ def dress(eng, uvs=False):
     eng.render_lights(light)
 
 
+def with_ibl(eng, label, base_ms):
+    """the frame as it is set up now, with the default environment; the environment is cleared again"""
+    eng.render_env_upload(128, 8, sge.ibl_default_env(128))
+    eng.render_brdf_lut_upload(sge.ibl_default_brdf_lut(128, 256))
+    ms = measure(eng, label, base_ms)
+    eng.render_ibl_clear()
+    return ms
+
+
 uniform_ms = measure(eng, "render_bench: %d x %d, %d characters + 17-Cheese (%d triangles) + %d boxes, opaque / mirror / glass materials, 2 lights" % (W, H, n, info.triangleCount, boxes))
+if "--ibl" in sys.argv:
+    with_ibl(eng, "(ibl) the same frame with specular IBL: the default 128 cube (8 levels) and 128 x 128 BRDF table", uniform_ms)
 if "--textures" in sys.argv:
     # the same context: uvs on every mesh, materials 3..5 = 0..2 for the characters (so that only they carry the normal map)
     dress(eng, uvs=True)
@@ -202,7 +216,9 @@ if "--textures" in sys.argv:
     bind["baseColor"] = 0
     bind["normal"][3:] = 1
     eng.render_material_textures(bind)
-    measure(eng, "(textures) the same frame, every material with a 256 x 256 sRGB base colour, the characters' also with a 256 x 256 normal map", uniform_ms)
+    textured_ms = measure(eng, "(textures) the same frame, every material with a 256 x 256 sRGB base colour, the characters' also with a 256 x 256 normal map", uniform_ms)
+    if "--ibl" in sys.argv:
+        with_ibl(eng, "(ibl, textures) the textured frame with specular IBL (the ratio is to the textured line)", textured_ms)
 eng.close()
 if "--variants" in sys.argv:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
